@@ -21,8 +21,14 @@ Modes for line (one process per GPU; torchrun sets RANK/LOCAL_RANK/WORLD_SIZE):
 Both: one 4-byte all_reduce(MAX) per step keeps the reference's global tooHigh exact; it runs on a
 side stream beside the merge, whose final correction pass alone waits for it (sdp.merge.AbsmaxAllReduce).
 Per-GPU work is fixed as N grows ("scaling": "weak").  `value` = all views x steps / max-over-
-ranks wall time.  The dominant conv class is timed live with HIP events on the forward's
-stream (roofline); the CPU baseline is the oracle restatement timed on this host (rank 0, N=1).
+ranks wall time.
+
+A plain run sets up, warms up, times --steps steps and prints the result line (`roofline`,
+`cpu_baseline`, `fp32_exact` and `sustained` of the sampling workloads are null).  --full adds the
+companion measurements, each a run of its own after the timed steps: the dominant conv class timed
+live with HIP events on the forward's stream (roofline), the sustained window, the exact-fp32 line
+and the CPU baseline (the oracle restatement timed on this host, rank 0, N=1).
+--dump-outputs DIR writes what the last timed step left (see dump_outputs).
 """
 from __future__ import annotations
 
@@ -72,11 +78,18 @@ def parse():
                     help="viewsplit on ONE GPU: merge against a megabatch this large (the other views' images stay "
                          "fixed) -- one rank's per-step work of BASELINE config 4 (32) without the all-gather")
     ap.add_argument("--precision", choices=["fp32x3", "fp32", "bf16"], default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the companion measurements: per-kernel rooflines (a "
+                         "profiled pass), the sustained window, the exact-fp32 line and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the arrays the last timed step produced as DIR/<name>.npy "
+                         "(float32/float64; a fixed seeded sample of what exceeds 60 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher check without a GPU: ranks join a gloo group and rank 0 prints the world it saw")
     ap.add_argument("--no-fp32-line", action="store_true",
-                    help="skip the exact-fp32 (v_mfma_f32_32x32x2_f32) companion measurement of the line workload")
+                    help="--full: skip the exact-fp32 (v_mfma_f32_32x32x2_f32) companion measurement of the line "
+                         "workload")
     ap.add_argument("--split", type=int, default=0,
                     help="part-batch streams per score-net forward (sdp_net_set_split; 0 = library default)")
     ap.add_argument("--unfused", action="store_true",
@@ -86,7 +99,7 @@ def parse():
     ap.add_argument("--fp32-tape", action="store_true",
                     help="train workload, bf16: keep the training tape in float32 (A/B against the bf16 tape)")
     ap.add_argument("--sustained-s", type=float, default=3.0,
-                    help="line/allforone: also time >= this many seconds of back-to-back steps after >= "
+                    help="--full, line/allforone: also time >= this many seconds of back-to-back steps after >= "
                          "--sustained-warm-s of warm load (the clock under MFMA load settles only after ~2 s; "
                          "0 = skip); reported as the `sustained` companion, the headline stays the K timed steps")
     ap.add_argument("--sustained-warm-s", type=float, default=2.0)
@@ -229,6 +242,30 @@ def overlap_of(kernel, classes):
             hid = sum(classes[c]["hidden_us"] for c in cl if c in classes)
             return round(hid / tot, 4) if tot else None
     return None
+
+
+# ----------------------------------------------------------------------------- output dump
+DUMP_BUDGET = 60 * 10 ** 6    # bytes of .npy payload per --dump-outputs directory (files stay under 64 MB)
+
+
+def dump_outputs(out_dir, arrays, rank=0):
+    """Write {name: tensor or ndarray} as out_dir/<name>.npy (ranks > 0: <name>_rank<r>.npy).  float64
+    stays float64, every other dtype is widened to float32.  When the arrays exceed DUMP_BUDGET in
+    all, each one larger than its equal share is replaced by a flat sample of its elements at fixed
+    indices (numpy default_rng(0), sorted), the same from run to run and from build to build."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        host[name] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+    if sum(a.nbytes for a in host.values()) > DUMP_BUDGET:
+        share = DUMP_BUDGET // len(host)
+        for name, a in host.items():
+            if a.nbytes > share:
+                idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+                host[name] = a.reshape(-1)[idx]
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + (f"_rank{rank}" if rank else "") + ".npy"), a)
 
 
 # ----------------------------------------------------------------------------- timing harness
@@ -376,9 +413,9 @@ def run_sampling(args, rank, N, dist, dev):
     merge_bytes = n_src * (8 * HWp + 8 * HWp + 2 * HWp) + V * (8 * HWp + 2 * 24 * ((50 * H) // 28) * W)
     merge_ev = None
 
-    def measure(prec, steps, warmup):
-        """Time `steps` steps with the score net at conv arithmetic `prec` (profiling OFF), then a
-        separate profiled pass of a few steps for the per-kernel rooflines; return (dt, roofline)."""
+    def measure(prec, steps, warmup, after_timed=None):
+        """Time `steps` steps with the score net at conv arithmetic `prec` (profiling OFF), then (--full)
+        a separate profiled pass of a few steps for the per-kernel rooflines; return (dt, roofline)."""
         net_box[0] = net if prec == args.precision else ScoreNet(H=H, W=W, precision=prec).load_synthetic()
         cur = net_box[0]
         if args.split:
@@ -387,6 +424,10 @@ def run_sampling(args, rank, N, dist, dev):
         for i in range(warmup):
             step(i)
         dt = timed(step, argparse.Namespace(warmup=0, steps=steps), dist, dev)
+        if after_timed is not None:
+            after_timed()
+        if not args.full:
+            return dt, None
         psteps = min(steps, 5)
         cur.profile(True)
         cur.profile_read()
@@ -444,10 +485,15 @@ def run_sampling(args, rank, N, dist, dev):
                         clock_source=clk["source"])
         return dt, roof
 
+    def dump():
+        # what the last timed step left: the megabatch images (own views updated and merged) and the
+        # own views' likelihood gradient
+        dump_outputs(args.dump_outputs, {"x": x_all, "likelihood_grad": lik}, rank)
+
     net_box = [net]
-    dt, roof = measure(args.precision, args.steps, args.warmup)
+    dt, roof = measure(args.precision, args.steps, args.warmup, dump if args.dump_outputs else None)
     sustained = None
-    if args.sustained_s > 0:
+    if args.full and args.sustained_s > 0:
         # dt is the max over ranks, so every rank derives the same step counts (no collective mismatch)
         per = dt / args.steps
         n_warm = max(1, int(np.ceil(args.sustained_warm_s / per)))
@@ -475,7 +521,7 @@ def run_sampling(args, rank, N, dist, dev):
                                        "frac": round(sfl / s_avg / 1e12 / PEAK[args.precision], 4)},
                      "note": "back-to-back steps after >= 2 s of warm load (steady DVFS clock), same step as value"}
     exact = None
-    if args.workload == "line" and args.precision != "fp32" and not args.no_fp32_line:
+    if args.full and args.workload == "line" and args.precision != "fp32" and not args.no_fp32_line:
         k = min(args.steps, 5)
         dt32, roof32 = measure("fp32", k, 1)
         exact = {"value": round(N * V * k / dt32, 3), "ms_per_step": round(dt32 / k * 1e3, 3), "steps": k,
@@ -486,7 +532,7 @@ def run_sampling(args, rank, N, dist, dev):
         return None
     value = N * V * args.steps / dt
     cpu = None
-    if N == 1 and not args.no_cpu_baseline:
+    if args.full and N == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(V, H, W, args.cpu_threads, args.workload)
     if args.workload == "allforone":
         wl = ("Inpainting.yml AllForOne simultaneous sampling step (score-net fwd + Langevin update + origin-offset "
@@ -530,6 +576,10 @@ def run_train(args, rank, N, dist, dev):
     dt = timed(step, args, dist, dev)
     if not all(np.isfinite(float(v)) for v in losses):
         raise SystemExit("non-finite training loss")
+    if args.dump_outputs:
+        # what the last timed train_step returned (loss, X_next) and the weights it left
+        dump_outputs(args.dump_outputs, {"loss": torch.as_tensor(losses[-1]).reshape(1), "x": state["X"],
+                                         "params": tr.params}, rank)
     if rank != 0:
         return None
     value = N * Bg * args.steps / dt
@@ -540,7 +590,7 @@ def run_train(args, rank, N, dist, dev):
             "unit": "TFLOP/s", "frac": round(achieved / PEAK[args.precision], 4), "traffic": None,
             "kernel": "whole training step (conv fwd + dgrad + wgrad FLOPs / step time)"}
     cpu = None
-    if N == 1 and not args.no_cpu_baseline:
+    if args.full and N == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline_train(H, W, args.cpu_threads)
     return {"metric": TRAIN_METRIC, "value": round(value, 3), "unit": "image-steps/s", "n_gpus": N,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True,
@@ -652,6 +702,12 @@ def run_project(args, rank, N, dist, dev):
     e1.synchronize()
     dev_ms_per_view = e0.elapsed_time(e1) / (args.steps * V)
     assert all(bool(torch.isfinite(r["real"]).all()) for r in out)
+    if args.dump_outputs:
+        # the V views the last timed step rendered: view and goal images, no-return and sky masks
+        dump_outputs(args.dump_outputs, {"real": torch.stack([r["real"] for r in out]),
+                                         "goal": torch.stack([r["goal"] for r in out]),
+                                         "no_return_mask": torch.stack([r["nm"] for r in out]),
+                                         "sky_mask": torch.stack([r["ns"] for r in out])}, rank)
     if rank != 0:
         return None
     # algorithmic bytes per view: transform 16 B in + 32 B out per point; per projection two
@@ -666,7 +722,7 @@ def run_project(args, rank, N, dist, dev):
                       "HIP events on the launch stream",
             "algorithmic_bytes_per_view": view_bytes, "avg_view_us": round(dev_ms_per_view * 1e3, 2)}
     cpu = None
-    if N == 1 and not args.no_cpu_baseline:
+    if args.full and N == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline_project(H, W, NP)
     return {"metric": PROJECT_METRIC, "value": round(N * V * args.steps / dt, 2), "unit": "views/s", "n_gpus": N,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),

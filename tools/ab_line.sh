@@ -8,7 +8,7 @@ IFS=';' read -r -a ARMV <<< "$ARMS"
 for round in ${ROUNDS:-1 2}; do
   for arm in "${ARMV[@]}"; do
     IFS='|' read -r name envs args <<< "$arm"
-    env $envs timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-fp32-line --sustained-s 3 $args \
+    env $envs timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-fp32-line --sustained-s 3 $args \
       > gpurun_out/ab/${name}_$round.log 2>&1 || { echo "arm $name failed rc=$?"; tail -5 gpurun_out/ab/${name}_$round.log; exit 1; }
     python3 - "$name" "$round" gpurun_out/ab/${name}_$round.log <<'PY'
 import json, sys

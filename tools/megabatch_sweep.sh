@@ -5,7 +5,7 @@
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 for mb in 4 8 16 32; do
-  timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-fp32-line --sustained-s 0 --megabatch-views $mb \
+  timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-fp32-line --sustained-s 0 --megabatch-views $mb \
     > gpurun_out/mb_$mb.log 2>&1 || { tail -3 gpurun_out/mb_$mb.log; exit 1; }
   python - gpurun_out/mb_$mb.log <<'PY'
 import json, sys

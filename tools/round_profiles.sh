@@ -23,12 +23,12 @@ step traffic 200 env ROUND=${ROUND:-r05} bash tools/class_traffic.sh
 step clock 500 env ROUND=${ROUND:-r05} bash tools/conv_clock.sh
 fi
 if [ "$PART" = 2 ] || [ "$PART" = all ]; then
-step bench 300 python bench.py --steps 20 --warmup 5
-step bench_views8 200 python bench.py --steps 10 --warmup 2 --views 8 --no-cpu-baseline --no-fp32-line
-step bench_mb32 200 python bench.py --steps 10 --warmup 2 --megabatch-views 32 --no-cpu-baseline --no-fp32-line
-step bench_allforone 300 python bench.py --workload allforone --steps 10 --warmup 2
-step bench_train 300 python bench.py --workload train --steps 10 --warmup 2
-step bench_project 200 python bench.py --workload project --steps 10 --warmup 2
+step bench 300 python bench.py --full --steps 20 --warmup 5
+step bench_views8 200 python bench.py --full --steps 10 --warmup 2 --views 8 --no-cpu-baseline --no-fp32-line
+step bench_mb32 200 python bench.py --full --steps 10 --warmup 2 --megabatch-views 32 --no-cpu-baseline --no-fp32-line
+step bench_allforone 300 python bench.py --full --workload allforone --steps 10 --warmup 2
+step bench_train 300 python bench.py --full --workload train --steps 10 --warmup 2
+step bench_project 200 python bench.py --full --workload project --steps 10 --warmup 2
 fi
 if [ "$PART" = 3 ] || [ "$PART" = all ]; then
 step rocprof 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-fp32-line --split 1 --sustained-s 0
