@@ -112,6 +112,10 @@ struct ConvArgs {
   // 1: every activation tensor of the launch (in, out, res, res2, out2, up, aux) holds bf16 elements
   // (the bf16 training tape, train.hip; bf16 mode); the launchers pick the IO16 instantiation
   int io16;
+  // 1: the ConvMeanPool 3x3 (zero-padded conv + 2x2 mean) as one 4x4 stride-2 conv (conv_kernel.h S2): wf16 holds
+  // the merged weights "#pool4x4" (train_aux.hip pack_slot16p); H, W are the input's, out is [B][H/2][W/2][Cout]
+  // and the statistics are those of its 128-pixel tiles.  The sampling forward in the bf16 modes only
+  int s2;
 };
 
 // Arguments of one weight-gradient launch (wgrad.hip).

@@ -96,6 +96,19 @@ hipError_t conv_mfma(int mode, ConvArgs a, int ks, bool pool, hipStream_t st, co
   if (!a.circular && d != 1) { *why = "conv: zero padding only for d=1"; return hipErrorInvalidValue; }
   if (!a.pro_ss) { *why = "conv: prologue scale/shift table missing"; return hipErrorInvalidValue; }
   if (a.Cin > 1024 && a.ss_bstride == 0) { *why = "conv: identity table holds 1024 channels"; return hipErrorInvalidValue; }
+  if (a.s2) {   // the ConvMeanPool 3x3 as a 4x4 stride-2 conv (conv_kernel.h S2): 8 x 16 tiles of the half-resolution output
+    if (!sh16 || a.io16 || ks != 3 || pool || d != 1 || a.circular || a.up || a.pro_mode == PRO_NONE || a.dact ||
+        (a.H % 16) || (a.W % 32)) {
+      *why = "conv: the 4x4 stride-2 form needs a bf16 mode, a zero-padded 3x3 with an ELU prologue, H%16 and W%32";
+      return hipErrorInvalidValue;
+    }
+#ifndef SDP_CONV_BENCH_ONLY   // (tools/conv_bench instantiates the 3x3 ELU-prologue shapes only)
+    return mode == MODE_F32X3 ? conv_launch_s2<MODE_F32X3>(a, st) : conv_launch_s2<MODE_BF16>(a, st);
+#else
+    *why = "conv: the 4x4 stride-2 form is not built into conv_bench";
+    return hipErrorInvalidValue;
+#endif
+  }
   if (a.io16) {   // the bf16 training tape: the shapes the training plan launches (conv_launch.h IO16)
 #ifdef SDP_CONV_BENCH_ONLY   // tools/conv_bench io16: the 16-wide ELU-prologue tiles only
     if (mode == MODE_BF16 && ks == 3 && tc == 16 && !pool) return conv_launch_nj2<MODE_BF16, true, 4, true>(a, st);

@@ -6,6 +6,7 @@
 //             of conv_launch_nj2 on 4 / 8 waves)
 //   dgrad 2-wave workgroups: code = 1000 + 10 * mode + 6; 32-Cout waves on 4 / 8 waves: + 7 / + 8
 //   dgrad   : code = 1000 + 10 * mode + shape                (shape = index into DgradShape)
+//   forward ConvMeanPool 3x3 as a 4x4 stride-2 conv (conv_launch_s2): code = 4000 + mode
 // Without SDP_INST (tools/conv_bench, -DSDP_CONV_BENCH_ONLY) it instantiates the 3x3 non-pooled
 // ELU-prologue forward shapes of every mode, which is all that bench dispatches.
 #include "conv_kernel.h"
@@ -85,6 +86,22 @@ hipError_t conv_launch_nj2(ConvArgs a, hipStream_t st) {
   return hipGetLastError();
 }
 
+// the ConvMeanPool 3x3 as a 4x4 stride-2 conv: tiles of 8 x 16 output pixels, the grid and the statistics groups
+// are those of the half-resolution output
+template <int MODE>
+hipError_t conv_launch_s2(ConvArgs a, hipStream_t st) {
+  using T = ConvTile<1, 16, 3, 4, 2>;
+  const int Ho = a.H / 2, Wo = a.W / 2;
+  a.tiles_per_img = Ho * Wo / (T::TR * 16);
+  a.groups_per_img = Ho * Wo / 128;
+  a.cpair = (SDP_CONV_CPAIR && a.Cout == 2 * T::NTILE) ? 1 : 0;
+  a.strip_w = a.cpair ? conv_strip_w(Ho / T::TR, Wo / 16) : 0;
+  dim3 grid(a.B * a.tiles_per_img * (a.cpair ? 2 : 1), a.cpair ? 1 : a.Cout / T::NTILE);
+  hipLaunchKernelGGL((conv_mfma_kernel<MODE, 1, 16, 3, false, true, true, 16, 4, false, 2, false, true>), grid, dim3(T::NTH),
+                     0, st, a);
+  return hipGetLastError();
+}
+
 template <int MODE, int WM, int TC, int KS, bool ZP, bool IO16>
 hipError_t dgrad_launch(ConvArgs a, hipStream_t st) {
   using T = ConvTile<WM, TC, KS, 4, 4, IO16>;
@@ -139,7 +156,10 @@ template <> struct DgradShape<3> { static constexpr int WM = 1, TC = 64, KS = 3;
 template <> struct DgradShape<4> { static constexpr int WM = 1, TC = 32, KS = 3; static constexpr bool ZP = false; };
 template <> struct DgradShape<5> { static constexpr int WM = 1, TC = 16, KS = 3; static constexpr bool ZP = false; };  // 16x16 shape only
 
-#if defined(SDP_INST) && SDP_INST >= 3000   // IO16 data gradients (bf16 tape): 0 = 1x1, 1 = zero-padded 3x3, 7 / 8 = 32-Cout waves on 4 / 8
+#if defined(SDP_INST) && SDP_INST >= 4000   // the 4x4 stride-2 ConvMeanPool forward: 4000 + mode (fp32x3, bf16)
+static_assert(SDP_INST - 4000 == MODE_F32X3 || SDP_INST - 4000 == MODE_BF16, "SDP_INST: bad 4x4 stride-2 code");
+template hipError_t conv_launch_s2<SDP_INST - 4000>(ConvArgs, hipStream_t);
+#elif defined(SDP_INST) && SDP_INST >= 3000   // IO16 data gradients (bf16 tape): 0 = 1x1, 1 = zero-padded 3x3, 7 / 8 = 32-Cout waves on 4 / 8
 constexpr int kS = SDP_INST % 10;
 static_assert(kS == 0 || kS == 1 || kS == 7 || kS == 8, "SDP_INST: bad IO16 dgrad code");
 #if SDP_INST % 10 == 0

@@ -2,7 +2,9 @@
 //
 // Covers every 3x3 conv of NCSN_LiDAR_small except begin/end conv:
 //   conv3x3 circular (LiDARGen/models/layers.py:37-44), dilated_conv3x3 circular
-//   (layers.py:55-60), ConvMeanPool 3x3/1x1 zero-pad + 2x2 mean (layers.py:291-313).
+//   (layers.py:55-60), ConvMeanPool 3x3/1x1 zero-pad + 2x2 mean (layers.py:291-313) -- the 3x3 one as conv-then-pool
+//   (exact fp32, training) or, in the sampling forward of the bf16 modes, as ONE 4x4 stride-2 conv on merged weights
+//   (template parameter S2 below: 16 taps on a quarter of the pixels instead of 9 on all of them).
 //
 // GEMM view: M = output pixels, N = Cout, K = taps x Cin.  One workgroup = 4 waves, ONE wave
 // per SIMD (512-register budget, accumulators in AGPRs); each wave owns 128 px x 64 Cout =
@@ -20,8 +22,10 @@
 //           taps 0..3 transform raw -> patch[(k+1)&1] (consumer prologue: InstanceNorm++
 //           affine and/or ELU, zero padding, bf16 hi/lo split) and the taps 4..8 issue the
 //           LDS-DMA of chunk k+2 into raw.
-//   weights: pre-arranged on the host in MFMA fragment order, streamed from L2 into VGPRs
-//           one tap ahead (buffer_load_b128 with a scalar per-(chunk, tap) offset).
+//   weights: pre-arranged on the device in MFMA fragment order (train_aux.hip), streamed from L2 into VGPRs
+//           a tap or more ahead (buffer_load_b128 with a scalar per-(chunk, tap) offset).
+//   S2     : the K loop runs 4 input phases x Cin/32 chunks of 4 taps each (2 x 2 of the 3 x 3 patch positions,
+//           compile-time per phase) through the same tap schedule; a 4-slot weight ring, slot = tap % 4.
 //
 // MODE_F32   : v_mfma_f32_32x32x2_f32 on fp32 operands (exact fp32 products).
 // MODE_F32X3 : operands split x = hi + lo (bf16 each), acc += hi*hi + hi*lo + lo*hi on
@@ -57,6 +61,11 @@ namespace sdp {
 #ifndef SDP_STORE_AUX16   // the bf16-tape (IO16) epilogues
 #define SDP_STORE_AUX16 SDP_STORE_AUX
 #endif
+
+#ifndef SDP_S2_RING   // weight-ring slots of the 4x4 stride-2 kernel (build-time A/B: 2 or 4 -- they divide its 4 taps).
+#define SDP_S2_RING 4 // 2 -> 4 (prefetch distance 1 -> 3 taps, 210 -> 242 VGPRs, still two waves per SIMD): 181.2 -> 168.9 us
+#endif                // per fp32x3 B=4 launch in the profiled pass; the line step could not tell them apart (374.3-375.6
+                      // vs 374.8-375.5 image-steps/s, profiles/experiments/r07_pool4x4_ring_ab.log)
 
 #ifdef SDP_TIMING   // tools/conv_bench: per-workgroup phase clocks of wave 0 into a.dbg
 #define SDP_T(i) do { if (tid == 0) tclk[i] = __builtin_amdgcn_s_memtime(); } while (0)
@@ -129,6 +138,16 @@ struct XformPlan {
   static constexpr int stage_blk(int q, int Q, int NBLK) { return 2 + q * (NBLK - 2) / (Q > 0 ? Q : 1); }
 };
 
+// The 4x4 stride-2 conv (conv_mfma_kernel S2) on the input phase (rho, gamma) = (phase / 2, phase % 2): output pixel
+// (i, j) takes input rows 2i - 1 + u, u = 0..3, i.e. row i - 1 (u = 0) and i (u = 2) of the rho = 1 sub-grid and rows
+// i (u = 1) and i + 1 (u = 3) of the rho = 0 sub-grid, columns likewise.  Tap t = 2 a + b of a phase's 2 x 2 taps sits
+// at patch position 3 kh + kw (the 3x3 kernel's numbering: kh - 1, kw - 1 = the sub-grid offset) and carries the
+// merged weight W4[u][v], u = 2 a + 1 - rho, v = 2 b + 1 - gamma.
+constexpr int s2_pos(int phase, int t) {
+  const int rho = phase >> 1, gamma = phase & 1;
+  return ((rho ? 0 : 1) + (t >> 1)) * 3 + (gamma ? 0 : 1) + (t & 1);
+}
+
 // SH: MFMA shape of the bf16 modes -- 32 = v_mfma_f32_32x32x16_bf16 (wave tile = 4 x 2 fragments
 // of 32 px x 32 Cout, two 16-deep k steps per 32-channel chunk), 16 = v_mfma_f32_16x16x32_bf16
 // (8 x 4 fragments of 16 px x 16 Cout, one 32-deep k step per chunk).  Same cycles per FLOP; the
@@ -146,8 +165,14 @@ struct XformPlan {
 // IO16 (the bf16 training tape, bf16 mode only): every activation tensor of the launch -- in, out, res, res2,
 // out2, up, aux -- holds bf16 elements: 16-B staging units of 8 channels (half the patch DMA bytes), bf16
 // epilogue loads and stores; statistics, bias and accumulation stay float32.
+// S2 (the sampling forward's ConvMeanPool 3x3, bf16 modes): the 2x2 mean of the zero-padded 3x3 conv as ONE 4x4 stride-2
+// conv with merged weights (train_aux.hip pack_slot16p, "#pool4x4"): 16 taps on a quarter of the pixels instead of 9
+// on all of them.  The tile is 8 x 16 OUTPUT (half-resolution) pixels; the K loop runs over the four (row, column)
+// parity phases of the full-resolution input -- half-resolution sub-grids, addressed as the dilation-2 sub-grids are,
+// the phase in the DMA's scalar offset -- and every (phase, 32-channel chunk) takes the 2 x 2 taps of its phase out
+// of the same 10 x 18 patch container (s2_pos).  No pooling is left in the epilogue.
 template <int MODE, int WM, int TC, int KS, bool POOL, bool ZP, bool PELU, int SH = 32, int NW = 4, bool TRN = false,
-          int NJ = 4, bool IO16 = false>
+          int NJ = 4, bool IO16 = false, bool S2 = false>
 __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(ConvArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)  // buffer-resource builtins exist only in the device pass
   static_assert(!IO16 || MODE == MODE_BF16, "the bf16 tape runs in bf16 mode");
@@ -161,9 +186,10 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
   static_assert((SH == 32) == (MODE == MODE_F32), "bf16 modes: 16x16 shape; exact fp32: 32x32");
   static_assert(NW == 4 || (SH == 16 && !POOL), "2-wave workgroups: the 16x16 non-pooled forward only");
   static_assert(NJ == 4 || (SH == 16 && !POOL && KS == 3 && WM == 1), "32-Cout waves: the 16x16 3x3 tiles only");
+  static_assert(!S2 || (NJ == 2 && NW == 4 && TC == 16 && ZP && !TRN && !IO16), "4x4 stride-2: zero-padded 32-Cout-wave tiles");
   using T = ConvTile<WM, TC, KS, NW, NJ, IO16>;
   constexpr int NTH = T::NTH;
-  constexpr int NT = KS * KS;
+  constexpr int NT = S2 ? 4 : KS * KS;            // taps per K chunk
   constexpr bool TRANS = TRN && SH == 16 && !POOL;
   constexpr int NU = T::NU;
   constexpr int XT = NT >= 4 ? 4 : NT;            // taps that carry the transform of the next chunk
@@ -178,7 +204,7 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
 #endif
   SDP_T(0);
   const int wm = WM == 1 ? 0 : (wave & 1), wn = WM == 1 ? wave : (wave >> 1);
-  const int d = a.dil, Hs = a.H / d, Ws = a.W / d;
+  const int d = S2 ? 2 : a.dil, Hs = a.H / d, Ws = a.W / d;   // (S2: a tile always has phase (0, 0))
   const int tiles_c = Ws / TC, tiles_rc = (Hs / T::TR) * tiles_c;
   // XCD-aware order: workgroups are dealt round-robin to the 8 XCDs, so give each XCD a
   // contiguous range of tiles -- vertically adjacent tiles share their halo rows in its L2
@@ -207,7 +233,8 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
   const int wrow0 = wm * T::RW;                    // wave's first tile row
 
   const int Cin = a.Cin, Cout = a.Cout;
-  const int nchunks = Cin / 32;
+  const int nck = Cin / 32;                        // 32-channel chunks of the input
+  const int nchunks = S2 ? 4 * nck : nck;          // K chunks (S2: per input phase)
   const int NB = Cout / 32;
   const int f0 = n0 / 16 + wn * NJ;                // global 16-channel fragment of this wave's nj = 0
   const int nbg0 = f0 / 2;                         // global 32-channel block of this wave's nb=0
@@ -244,7 +271,8 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
   // of 3, so the slot of (chunk, tap) is tap % 3 in every chunk; 2 deep for the 1x1 conv (a 9-slot
   // ring for the hi-only bf16 fragments measured 135.5 -> 134.4 image-steps/s in the bf16 training
   // step, profiles/experiments/r03_train_ring_wgrad_ab.log)
-  constexpr int NBUF = (NT % 3 == 0) ? 3 : 2;
+  // S2 (4 taps, the tap schedule): a ring of SDP_S2_RING = 2 or 4 slots, slot = tap % ring, prefetch distance ring - 1
+  constexpr int NBUF = S2 ? SDP_S2_RING : (NT % 3 == 0) ? 3 : 2;
   uint4 bq[NBUF][NJ / 2][4];   // SH 32: [slot][nb][(s, hi/lo)]; SH 16: [slot][nj / 2][(nj % 2, hi/lo)]
   // SH 16: fragment nj (Couts 16 nj .. of the wave's 64) lane l needs Cout 16 nj + l % 16 and
   // channel group g = l / 16 (channels 8g .. 8g+7 of the chunk); the 32x32 packing stores Cout c,
@@ -289,6 +317,24 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
   // (scale, shift) rows of this image (the identity table when there is no affine prologue):
   // consumed only by the next chunk's transform, so the loads stay in flight across a chunk
   const float* ssb = a.pro_ss + (size_t)b * a.ss_bstride;
+  // K chunk c -> the 32-channel chunk it reads (its (scale, shift) rows) and the scalar byte offset of its patch DMA.
+  // S2: the chunks run (phase 0, phase 1) x channel chunks, then (phase 2, phase 3) x channel chunks (phase = 2 x row
+  // parity + column parity), so the phase -- the tap set -- is a compile-time constant of the main loop's two chunk
+  // parities; the phase moves the patch by (row parity, column parity) full-resolution pixels.  Chunks past the
+  // last one (the dead transform / DMA of the loop's tail) repeat the last
+  auto chunk_cc = [&](int c) __attribute__((always_inline)) {
+    if constexpr (S2) return (c >= 2 * nck ? c - 2 * nck : c) >> 1;
+    else return c;
+  };
+  auto chunk_soff = [&](int c) __attribute__((always_inline)) {
+    if constexpr (S2) {
+      c = min(c, nchunks - 1);
+      const int rho = c >= 2 * nck ? 1 : 0, r = c - rho * 2 * nck;
+      return ((rho * a.W + (r & 1)) * Cin + (r >> 1) * 32) * ES;
+    } else {
+      return c * 32 * ES;
+    }
+  };
   const int my_cv = tid & (T::UPP - 1);            // every unit of a thread has cv == tid % UPP
   // (scale, shift) of this thread's CPU channels, double-buffered by chunk parity: chunk c's rows live
   // in ssv[c & 1][..] (the transform of chunk c writes patch buffer c & 1 too); float4 k = channels 2k, 2k+1
@@ -336,7 +382,7 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
     const int base = __builtin_amdgcn_readfirstlane(((tid & ~63) + k * NTH) * 16);
     __builtin_amdgcn_raw_ptr_buffer_load_lds(
         irs, reinterpret_cast<__attribute__((address_space(3))) void*>(reinterpret_cast<uintptr_t>(raw + base)), 16,
-        uoff[k], chunk * 32 * ES, 0, SDP_DMA_AUX);
+        uoff[k], chunk_soff(chunk), 0, SDP_DMA_AUX);
   };
   // the same DMA as inline asm (common.h dma16_lds_opaque), for the main loop of the 3x3 tap schedule:
   // the compiler cannot tell the raw slots apart and would wait for every DMA in flight (vmcnt(0))
@@ -348,7 +394,7 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
     constexpr int k = decltype(kc)::value;
     if constexpr (SDP_KO & 1) return;
     const uint32_t base = (uint32_t)(uintptr_t)(raw + ((tid & ~63) + k * NTH) * 16);
-    dma16_lds_opaque(irs_o, base, uoff[k], chunk * 32 * ES);
+    dma16_lds_opaque(irs_o, base, uoff[k], chunk_soff(chunk));
   };
   // transform staging unit k of raw into patch buffer PB
   // transform of staging unit k: raw (fp32, landed by this thread's own DMA) -> patch buffer PB
@@ -462,7 +508,7 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
   static_for<0, NU>([&](auto k) { load_unit(k, 0); });
   static_for<0, NU>([&](auto k) { xform_unit(k, std::integral_constant<int, 0>{}); });
   if (nchunks > 1) {
-    load_ss(std::integral_constant<int, 1>{}, 1);
+    load_ss(std::integral_constant<int, 1>{}, chunk_cc(1));
     static_for<0, NU>([&](auto k) { load_unit(k, 1); });
   }
   __syncthreads();
@@ -625,17 +671,18 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
   //   blocks 0, 1            : the raw values of the units this tap transforms (XformPlan::tap_of)
   //   blocks 2 .. 31         : their transform, 5 stages per 2-channel piece
   //   blocks 30, 31          : the LDS-DMA of those units for the chunk after next (raw slot free)
-  using XP = XformPlan<NU, NT, (MODE == MODE_BF16 && !IO16) ? 8 : 5>;   // (IO16: 4 pieces per unit)
+  // (IO16: 4 pieces per unit; S2: up to two units per tap)
+  using XP = XformPlan<NU, NT, (MODE == MODE_BF16 && !IO16 && !S2) ? 8 : 5>;
   constexpr int NQ = MODE == MODE_F32X3 ? 8 : 4;   // A reads per half tap
   constexpr int NWL = NJ * (MODE == MODE_F32X3 ? 2 : 1);   // weight loads per tap
   constexpr int NBLK = 8 * NJ;                     // MFMA blocks per tap: (half s, Cout fragment nj, px group i)
   static_assert(NQ <= NBLK / 2 && 2 * NWL <= NBLK, "the tap's fillers fit its blocks");
   using I0 = std::integral_constant<int, 0>;
   using I1 = std::integral_constant<int, 1>;
-  // one A fragment: pixel group i of half s of tap `tap`, hi (LO = 0) or lo part
-  auto read_a1 = [&](const char* pat, auto tap_c, auto s_c, auto i_c, auto lo_c) __attribute__((always_inline)) {
-    constexpr int tap = decltype(tap_c)::value, s = decltype(s_c)::value, i = decltype(i_c)::value;
-    constexpr int kh = tap / 3, kw = tap % 3, mb = 4 * s + i;
+  // one A fragment: pixel group i of half s of the tap at patch position pos = 3 kh + kw, hi (LO = 0) or lo part
+  auto read_a1 = [&](const char* pat, auto pos_c, auto s_c, auto i_c, auto lo_c) __attribute__((always_inline)) {
+    constexpr int pos = decltype(pos_c)::value, s = decltype(s_c)::value, i = decltype(i_c)::value;
+    constexpr int kh = pos / 3, kw = pos % 3, mb = 4 * s + i;
     constexpr int mr = mb / (TC / 16), mc = (mb % (TC / 16)) * 16;
     return *reinterpret_cast<const bf16x8*>(pat + ((wrow0 + mr + kh) * T::PC + mc + kw) * PSTRIDE + a_lane_off16 +
                                             (decltype(lo_c)::value ? 64 : 0));
@@ -649,22 +696,27 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
     const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(wrs, wq16[nj], so, 0);
     bq[J][nj >> 1][2 * (nj & 1) + part] = make_uint4(v.x, v.y, v.z, v.w);
   };
-  auto do_chunk9 = [&](auto parity, int chunk) __attribute__((always_inline)) {
-    constexpr int P = decltype(parity)::value;
+  // (PHS: the input phase of the chunk, S2 only -- the patch positions of its taps)
+  auto do_chunk9 = [&](auto parity, auto phase_c, int chunk) __attribute__((always_inline)) {
+    constexpr int P = decltype(parity)::value, PHS = decltype(phase_c)::value;
     const char* pat = lds + P * T::PATCH_BYTES;
     bf16x8 ca[2][4], cb[2][4];   // [hi, lo][i]: half s = 0 / s = 1 of the current tap
     static_for<0, 4>([&](auto i) {
-      ca[0][i] = read_a1(pat, I0{}, I0{}, i, I0{});
-      if constexpr (MODE == MODE_F32X3) ca[1][i] = read_a1(pat, I0{}, I0{}, i, I1{});
+      using POS0 = std::integral_constant<int, S2 ? s2_pos(PHS, 0) : 0>;
+      ca[0][i] = read_a1(pat, POS0{}, I0{}, i, I0{});
+      if constexpr (MODE == MODE_F32X3) ca[1][i] = read_a1(pat, POS0{}, I0{}, i, I1{});
     });
-    load_ss(std::integral_constant<int, P>{}, min(chunk + 2, nchunks - 1));   // buffer P: chunk-1's, free
+    load_ss(std::integral_constant<int, P>{}, chunk_cc(min(chunk + 2, nchunks - 1)));   // buffer P: chunk-1's, free
     static_for<0, NT>([&](auto tap_c) {
       constexpr int tap = decltype(tap_c)::value;
-      constexpr int CUR = tap % 3, NXT = (tap + 2) % 3;
+      constexpr int DIST = NBUF - 1;                     // weight prefetch distance in taps; ring slot = tap % NBUF
+      constexpr int CUR = tap % NBUF, NXT = (tap + DIST) % NBUF;
+      using POS = std::integral_constant<int, S2 ? s2_pos(PHS, tap) : tap>;
+      using POSN = std::integral_constant<int, S2 ? s2_pos(PHS, tap + 1 < NT ? tap + 1 : 0) : tap + 1>;
       constexpr int U0 = XP::first(tap), UN = XP::count(tap), Q = COPY ? UN : UN * PPU * XP::NSTG;
       constexpr int UNA = UN > 0 ? UN : 1;
-      const int wchunk = tap + 2 < NT ? chunk : min(chunk + 1, nchunks - 1);
-      constexpr int wtap = tap + 2 < NT ? tap + 2 : tap + 2 - NT;
+      const int wchunk = tap + DIST < NT ? chunk : min(chunk + 1, nchunks - 1);
+      constexpr int wtap = tap + DIST < NT ? tap + DIST : tap + DIST - NT;
       float4 xr[UNA];                                  // raw values of this tap's units
       float py0[PPU * UNA], py1[PPU * UNA], pe0[PPU * UNA], pe1[PPU * UNA];
       uint32_t phi[PPU * UNA], plo[PPU * UNA];
@@ -796,13 +848,13 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
         // ---- fillers for later taps
         if constexpr (blk < NQ) {   // this tap's half-1 fragments (used from block NBLK / 2)
           constexpr int q = blk, ii = MODE == MODE_F32X3 ? (q >> 1) : q, lo = MODE == MODE_F32X3 ? (q & 1) : 0;
-          cb[lo][ii] = read_a1(pat, tap_c, I1{}, std::integral_constant<int, ii>{}, std::integral_constant<int, lo>{});
+          cb[lo][ii] = read_a1(pat, POS{}, I1{}, std::integral_constant<int, ii>{}, std::integral_constant<int, lo>{});
         }
         if constexpr ((blk & 1) && (blk >> 1) < NWL)   // tap + 2's weights
           load_b1(std::integral_constant<int, NXT>{}, std::integral_constant<int, (blk >> 1)>{}, wchunk, wtap);
         if constexpr (tap + 1 < NT && blk >= NBLK / 2 && blk < NBLK / 2 + NQ) {   // tap + 1's half-0 fragments
           constexpr int q = blk - NBLK / 2, ii = MODE == MODE_F32X3 ? (q >> 1) : q, lo = MODE == MODE_F32X3 ? (q & 1) : 0;
-          ca[lo][ii] = read_a1(pat, std::integral_constant<int, tap + 1>{}, I0{}, std::integral_constant<int, ii>{},
+          ca[lo][ii] = read_a1(pat, POSN{}, I0{}, std::integral_constant<int, ii>{},
                                std::integral_constant<int, lo>{});
         }
         static_for<0, Q>([&](auto q_c) {   // transform stages dealt to this block
@@ -821,17 +873,30 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
     __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0)
     if constexpr (!(SDP_KO & 8)) __builtin_amdgcn_s_barrier();
   };
-  static_assert(NT % 2 == 1, "parity bookkeeping assumes an odd tap count");
+  // do_chunk's 2-slot weight ring alternates with the chunk parity, which assumes an odd tap count; the tap
+  // schedule's slot is tap % NBUF, the same in every chunk when NBUF divides the tap count (9 = 3 x 3, S2: 4 = 2 x 2)
+  static_assert(NT % 2 == 1 || (S2 && NT % NBUF == 0), "weight-ring slots repeat from chunk to chunk");
   // (the data-gradient launches keep do_chunk: in bf16 training the tap schedule measured 3-5 % slower
   // on them, profiles/experiments/r05_train_kernel_stats_ab.log)
 #ifndef SDP_DGRAD16_TAPS   // A/B (build-time): the IO16 data gradient on the tap schedule -- measured slower,
 #define SDP_DGRAD16_TAPS 0    // bf16-tape training 181.0-181.5 -> 177.6-177.8 image-steps/s (profiles/experiments/r06_dgrad16_taps_ab.log)
 #endif
-  if constexpr (MODE != MODE_F32 && NT == 9 && (!TRANS || (IO16 && SDP_DGRAD16_TAPS))) {
+  if constexpr (S2) {
+    static_assert(MODE != MODE_F32 && NT % NBUF == 0, "4x4 stride-2: the tap schedule of the bf16 modes");
+    static_assert(XP::max_count() * PPU * XP::NSTG <= 2 * (NBLK - 2), "at most two transform stages per block");
+    for (int chunk = 0; chunk < 2 * nck; chunk += 2) {   // row parity 0: column parity = chunk parity
+      do_chunk9(I0{}, I0{}, chunk);
+      do_chunk9(I1{}, I1{}, chunk + 1);
+    }
+    for (int chunk = 2 * nck; chunk < nchunks; chunk += 2) {   // row parity 1
+      do_chunk9(I0{}, std::integral_constant<int, 2>{}, chunk);
+      do_chunk9(I1{}, std::integral_constant<int, 3>{}, chunk + 1);
+    }
+  } else if constexpr (MODE != MODE_F32 && NT == 9 && (!TRANS || (IO16 && SDP_DGRAD16_TAPS))) {
     static_assert(XP::max_count() * PPU * XP::NSTG <= 2 * (NBLK - 2), "at most two transform stages per block");
     for (int chunk = 0; chunk < nchunks; chunk += 2) {   // nchunks is even (Cin % 64 == 0)
-      do_chunk9(std::integral_constant<int, 0>{}, chunk);
-      do_chunk9(std::integral_constant<int, 1>{}, chunk + 1);
+      do_chunk9(I0{}, I0{}, chunk);
+      do_chunk9(I1{}, I0{}, chunk + 1);
     }
   } else {
     for (int chunk = 0; chunk < nchunks; chunk += 2) {
@@ -1025,7 +1090,8 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
     // of channels.  ConvMeanPool pairs registers r, r+1 (columns) and fragments mb, mb + TC/16
     // (rows); the 128-pixel InstanceNorm++ group of a channel spans the 4 lanes l % 16 + 16q.
     __builtin_amdgcn_s_waitcnt(0);   // the last (dead) DMA may still be landing in raw
-    const int Ho = POOL ? a.H / 2 : a.H, Wo = POOL ? a.W / 2 : a.W;
+    const int Ho = (POOL || S2) ? a.H / 2 : a.H, Wo = (POOL || S2) ? a.W / 2 : a.W;
+    const int de = S2 ? 1 : d;                       // pixel step of the output (S2: the tile's own half-resolution grid)
     const size_t bo = (size_t)b * Ho * Wo * Cout;
     const int img_bytes = Ho * Wo * Cout * ES;
     auto rs = [&](const float* p) {
@@ -1038,7 +1104,7 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
     constexpr int NF = POOL ? CB : 8;                // fragments (pooled: row-0 fragments) per lane
     constexpr int PER = POOL ? 2 : 4;                // values per fragment and lane
     constexpr int NV = NF * PER;
-    const int xs = (POOL ? 1 : d) * Cout * ES;       // bytes between consecutive output pixels of a run
+    const int xs = (POOL ? 1 : de) * Cout * ES;      // bytes between consecutive output pixels of a run
     // byte offset of value i of channel block nj: a per-fragment VGPR base (channel block 0) and a
     // wave-uniform SGPR part (the value's pixel step, the block's 64-B channel offset)
     int vbase[NF];
@@ -1049,7 +1115,7 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
         vbase[f] = (((sr0 >> 1) * Wo + ((sc0 + f * 16) >> 1) + 2 * lq) * Cout + co) * ES;
       } else {
         constexpr int mr = f / CB, mc = (f % CB) * 16;
-        const int y = (sr0 + wrow0 + mr) * d + ph_r, x = (sc0 + mc + 4 * lq) * d + ph_c;
+        const int y = (sr0 + wrow0 + mr) * de + ph_r, x = (sc0 + mc + 4 * lq) * de + ph_c;
         vbase[f] = ((y * Wo + x) * Cout + co) * ES;
       }
     });
@@ -1119,7 +1185,7 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
           for (int r = 0; r < 4; ++r) v[f * 4 + r] = acc4[f][nj][r] + bias;
         });
       }
-      if (a.up) {   // F.interpolate(bilinear, align_corners=True) of a [H/2][W/2] tensor (non-pooled)
+      if (!S2 && a.up) {   // F.interpolate(bilinear, align_corners=True) of a [H/2][W/2] tensor (non-pooled)
         const int Hi = a.H / 2, Wi = a.W / 2;
         const float shh = (float)(Hi - 1) / (float)(a.H - 1), sww = (float)(Wi - 1) / (float)(a.W - 1);
         const size_t ub = (size_t)b * Hi * Wi * Cout + co;
@@ -1128,7 +1194,7 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
         for (int i = 0; i < NV; ++i) {
           const int f = i / PER, k = i % PER;
           const int mr = f / CB, mc = (f % CB) * 16;
-          const int y = (sr0 + wrow0 + mr) * d + ph_r, x = (sc0 + mc + 4 * lq + k) * d + ph_c;
+          const int y = (sr0 + wrow0 + mr) * de + ph_r, x = (sc0 + mc + 4 * lq + k) * de + ph_c;
           const float fy = shh * (float)y, fx = sww * (float)x;
           const int y0 = (int)fy, x0 = (int)fx;
           const int yp = y0 < Hi - 1 ? 1 : 0, xp = x0 < Wi - 1 ? 1 : 0;

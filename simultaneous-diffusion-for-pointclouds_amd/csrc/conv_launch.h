@@ -21,6 +21,11 @@ hipError_t conv_launch_half(ConvArgs a, hipStream_t st);
 template <int MODE, bool PELU, int NW, bool IO16 = false>
 hipError_t conv_launch_nj2(ConvArgs a, hipStream_t st);
 
+// forward of the ConvMeanPool 3x3 as a 4x4 stride-2 conv (conv_kernel.h S2; ConvArgs::s2) on 8 x 16 output tiles and
+// 32-Cout waves: 4-wave 128-Cout workgroups, the 256 Couts as a pair per tile (conv_inst.hip codes 4000 + mode)
+template <int MODE>
+hipError_t conv_launch_s2(ConvArgs a, hipStream_t st);
+
 // data gradient of the 128-channel layers on 2-wave workgroups (conv_inst.hip dgrad shape 6)
 template <int MODE>
 hipError_t dgrad_launch_half(ConvArgs a, hipStream_t st);

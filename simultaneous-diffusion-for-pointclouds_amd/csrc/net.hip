@@ -46,6 +46,7 @@ struct Fwd {
     int dil = 1;
     bool circular = true;
     bool pool = false;
+    bool s2 = false;           // the ConvMeanPool 3x3 as one 4x4 stride-2 conv on the merged weights (bf16 modes)
   };
 
   void conv(const Buf& in, const std::string& wkey, const Buf& out, const Opt& o) {
@@ -54,7 +55,9 @@ struct Fwd {
     a.in = in.p;
     // forward weights: "#frag16" in the bf16 modes (16x16 MFMAs), "#frag" for exact fp32 (32x32)
     a.wf = net->mode == MODE_F32 ? reinterpret_cast<const uint4*>(net->P(wkey + ".weight#frag")) : nullptr;
-    a.wf16 = net->mode == MODE_F32 ? nullptr : reinterpret_cast<const uint4*>(net->P(wkey + ".weight#frag16"));
+    a.wf16 = net->mode == MODE_F32 ? nullptr
+                                   : reinterpret_cast<const uint4*>(net->P(wkey + (o.s2 ? ".weight#pool4x4" : ".weight#frag16")));
+    a.s2 = o.s2 ? 1 : 0;
     a.bias = o.bias ? net->P(wkey + ".bias") : nullptr;
     a.out = out.p;
     a.res = o.res;
@@ -82,6 +85,11 @@ struct Fwd {
                 std::to_string(out.C) + " @" + std::to_string(in.H) + "x" + std::to_string(in.W) + " d" +
                 std::to_string(o.dil) + (o.pool ? " pool" : "");
       rec.flops = 2.0 * B * in.H * in.W * (double)in.C * out.C * ks * ks;
+      if (o.s2) {   // the FLOPs it executes: 16 taps per output pixel (conv-then-pool, the algorithmic form: 36)
+        rec.cls = "conv4x4s2 " + std::to_string(in.C) + "->" + std::to_string(out.C) + " @" + std::to_string(in.H) + "x" +
+                  std::to_string(in.W);
+        rec.flops = 2.0 * B * out.H * out.W * (double)in.C * out.C * 16;
+      }
       rec.bytes = 4.0 * B * ((double)in.H * in.W * in.C + (double)out.H * out.W * out.C) + 4.0 * out.C * in.C * ks * ks;
       rec.a = net->event();
       rec.b = net->event();
@@ -129,6 +137,10 @@ struct Fwd {
   }
   static int tiles(const Buf& b) { return b.H * b.W / 128; }
 
+  // the ConvMeanPool 3x3 of a down-sampling block runs as one 4x4 stride-2 conv in the bf16 modes (conv_kernel.h S2):
+  // its statistics are then those of 128-pixel tiles of the OUTPUT (conv-then-pool: 32 pooled pixels per tile)
+  bool pool_as_s2() const { return net->mode != MODE_F32; }
+
   // ResidualBlock.forward (layers.py:443-456); returns output in `out`, stats of out written
   void resblock(const std::string& k, const Buf& x, const Buf& t1, const Buf& t2, const Buf& out, bool down, int dil,
                 bool want_stats, int x_tiles, float x_cnt) {
@@ -154,7 +166,8 @@ struct Fwd {
       os.circular = false;
       conv(xp, k + ".shortcut.conv", t2, os);
       o2.circular = false;
-      o2.pool = true;
+      o2.pool = !pool_as_s2();
+      o2.s2 = pool_as_s2();
       o2.res = t2.p;
       conv(t1, k + ".conv2.conv", out, o2);
     } else if (down) {
@@ -248,7 +261,8 @@ static void forward_impl(sdp_net* net, const float* x, const int64_t* labels, fl
   f.resblock("res1.1", FC, FB, FD, L1, false, 1, true, Fwd::tiles(FC), 128.f);
   // res2 (down: ConvMeanPool)
   f.resblock("res2.0", L1, FB, QA, QB, true, 1, true, Fwd::tiles(L1), 128.f);
-  f.resblock("res2.1", QB, QA, QC, L2, false, 1, true, Fwd::tiles(L1), 32.f);
+  if (f.pool_as_s2()) f.resblock("res2.1", QB, QA, QC, L2, false, 1, true, Fwd::tiles(QB), 128.f);
+  else f.resblock("res2.1", QB, QA, QC, L2, false, 1, true, Fwd::tiles(L1), 32.f);
   // res3 (dilation 2), res4 (dilation 4)
   f.resblock("res3.0", L2, QA, QB, QC, true, 2, true, Fwd::tiles(L2), 128.f);
   f.resblock("res3.1", QC, QA, QB, L3, false, 2, true, Fwd::tiles(QC), 128.f);

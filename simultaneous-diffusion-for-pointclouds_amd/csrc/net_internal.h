@@ -116,6 +116,13 @@ struct sdp_net {
     auto it = host.find(k);
     return it != host.end() && it->second.shape.size() == 4 && k != "begin_conv.weight" && k != "end_conv.weight";
   }
+  // the 3x3 conv of a ConvMeanPool (layers.py:291-313): conv2 of a down-sampling, undilated residual block
+  bool is_pool3x3_w(const std::string& k) const {
+    static const std::string suffix = ".conv2.conv.weight";
+    auto it = host.find(k);
+    return k.size() > suffix.size() && k.compare(k.size() - suffix.size(), suffix.size(), suffix) == 0 &&
+           it != host.end() && it->second.shape.size() == 4 && it->second.shape[2] == 3 && it->second.shape[3] == 3;
+  }
   // (re)build the fragment-ordered weights from the fp32 parameters on the device: one
   // launch over every conv (a descriptor table, re-uploaded when a parameter moves)
   std::vector<sdp::PackDesc> pack_host;
@@ -132,13 +139,16 @@ struct sdp_net {
       // "#dfrag16" (training: bf16 modes); (1 was the data gradient in 32x32 order -- read in 16-B pieces
       // at a 64-B lane stride, and in bf16 mode only the hi half of each 32 B: replaced in round 6 --
       // 2 the Winograd packing, removed with its kernel)
-      for (int dg = 0; dg < 5; ++dg) {
+      // 5 = "#pool4x4": the 3x3 of a ConvMeanPool merged with its 2x2 mean into a 4x4 stride-2 conv, 16 taps in
+      // 16x16 fragment order (the sampling forward, bf16 modes; train_aux.hip pack_slot16p)
+      for (int dg = 0; dg < 6; ++dg) {
         if (dg == 0 && mode != sdp::MODE_F32) continue;
         if (dg == 1 || dg == 2) continue;
         if (dg == 3 && mode == sdp::MODE_F32) continue;
         if (dg == 4 && (!train_packs || mode == sdp::MODE_F32)) continue;
-        const std::string fk = kv.first + (dg == 0 ? "#frag" : dg == 3 ? "#frag16" : "#dfrag16");
-        const int nt = (int)(s[2] * s[3]);
+        if (dg == 5 && (mode == sdp::MODE_F32 || !is_pool3x3_w(kv.first))) continue;
+        const std::string fk = kv.first + (dg == 0 ? "#frag" : dg == 3 ? "#frag16" : dg == 4 ? "#dfrag16" : "#pool4x4");
+        const int nt = dg == 5 ? 16 : (int)(s[2] * s[3]);
         const size_t n = (size_t)s[0] * s[1] * nt;
         if (!dev.count(fk)) {
           void* p = nullptr;

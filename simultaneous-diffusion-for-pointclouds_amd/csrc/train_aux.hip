@@ -83,6 +83,44 @@ SDP_DEV uint32_t pack_slot16(const float* __restrict__ w, int Cout, int Cin, int
   return pk;
 }
 
+// "#pool4x4": ConvMeanPool's zero-padded 3x3 conv + 2x2 mean (layers.py:291-313) merged into one 4x4 stride-2 conv,
+//   W4[co][ci][u][v] = 1/4 sum_{p, q in {0, 1}} W3[co][ci][u - p][v - q]   (terms outside 0..2 dropped),
+// summed in float32 in the fixed order (p, q) = (0,0), (0,1), (1,0), (1,1), and only then split into hi + lo; out(i, j)
+// = bias + sum_{u,v} W4[u][v] a(2i - 1 + u, 2j - 1 + v), a = 0 outside the image.  Packed in the 16x16 fragment
+// order above for the K loop of conv_mfma_kernel S2: chunk = (2 rho nck + 2 cc + gamma) over the input's (row,
+// column)-parity phases (rho, gamma) and its nck = Cin/32 channel chunks cc, 4 taps t = 2 a + b per chunk with
+// u = 2 a + 1 - rho, v = 2 b + 1 - gamma (conv_kernel.h s2_pos).  Slots: Cout * Cin * 16.
+SDP_DEV uint32_t pack_slot16p(const float* __restrict__ w, int Cout, int Cin, int mode, size_t i) {
+  const int NF = Cout / 16, nck = Cin / 32;
+  const int word = i & 3;
+  const int lane = (i >> 2) & 63;
+  const int hl = (i >> 8) & 1;
+  size_t r = i >> 9;
+  const int nf = r % NF;
+  r /= NF;
+  const int tap = r % 4;
+  const int ch = (int)(r / 4);
+  const int rho = ch >= 2 * nck ? 1 : 0, rr = ch - rho * 2 * nck, gamma = rr & 1, cc = rr >> 1;
+  const int u = 2 * (tap >> 1) + 1 - rho, v = 2 * (tap & 1) + 1 - gamma;
+  const int co = nf * 16 + (lane & 15);
+  uint32_t pk = 0;
+  for (int e = 0; e < 2; ++e) {
+    const int ci = cc * 32 + 8 * (lane >> 4) + word * 2 + e;
+    const float* w3 = w + ((size_t)co * Cin + ci) * 9;
+    float sum = 0.f;
+    for (int p = 0; p < 2; ++p)
+      for (int q = 0; q < 2; ++q) {
+        const int kh = u - p, kw = v - q;
+        if (kh >= 0 && kh < 3 && kw >= 0 && kw < 3) sum += w3[kh * 3 + kw];
+      }
+    const float f = 0.25f * sum;
+    const __bf16 hi = (__bf16)f;
+    const __bf16 qv = (hl && mode == MODE_F32X3) ? (__bf16)(f - (float)hi) : hi;
+    pk |= (uint32_t)__builtin_bit_cast(uint16_t, qv) << (16 * e);
+  }
+  return pk;
+}
+
 __global__ void pack_weights_kernel(const float* __restrict__ w, uint32_t* __restrict__ out, int Cout, int Cin, int NT,
                                     int mode, int dgrad) {
   const size_t n = (size_t)Cout * Cin * NT;    // output 32-bit slots
@@ -96,8 +134,9 @@ __global__ void pack_weights_multi_kernel(const PackDesc* __restrict__ d, int mo
   const PackDesc e = d[blockIdx.y];
   const size_t n = (size_t)e.Cout * e.Cin * e.NT;
   for (size_t j = blockIdx.x * (size_t)blockDim.x + threadIdx.x; j < n; j += (size_t)gridDim.x * blockDim.x)
-    e.out[j] = e.dgrad >= 3 ? pack_slot16(e.w, e.Cout, e.Cin, e.NT, mode, e.dgrad == 4, j)
-                            : pack_slot(e.w, e.Cout, e.Cin, e.NT, mode, e.dgrad, j);
+    e.out[j] = e.dgrad == 5   ? pack_slot16p(e.w, e.Cout, e.Cin, mode, j)
+               : e.dgrad >= 3 ? pack_slot16(e.w, e.Cout, e.Cin, e.NT, mode, e.dgrad == 4, j)
+                              : pack_slot(e.w, e.Cout, e.Cin, e.NT, mode, e.dgrad, j);
 }
 
 hipError_t pack_weights_multi(const PackDesc* d, int nd, size_t total, int mode, hipStream_t st) {

@@ -26,7 +26,8 @@ sys.path.insert(0, os.path.join(REPO, "simultaneous-diffusion-for-pointclouds_am
 # label, kernel-name substring, threads per view along x (grid x), grid y (Cout / 128), FLOP per view,
 # MFMA passes, conv_bench C.  Both classes run conv_launch_nj2's 4-wave 128-Cout workgroups (NJ = 2):
 # the 256-Cout layers as two per tile (grid y = 2)
-NJ2 = "conv_mfma_kernel<1, 1, 16, 3, false, false, true, 16, 4, false, 2, false>"   # (..., NJ, IO16)
+_NJ2 = "conv_mfma_kernel<1, 1, 16, 3, false, false, true, 16, 4, false, 2, false"    # (..., NJ, IO16
+NJ2 = (_NJ2 + ", false>", _NJ2 + ">")   # [, S2 = false]): the name with and without the kernel's last parameter
 CLASSES = [
     ("conv3x3 256->256 @32x512 d1", NJ2, 256 * 256, 1, 2 * 256 * 256 * 9 * 32 * 512, 3, 256),
     ("conv3x3 128->128 @64x1024 d1", NJ2, 512 * 256, 1, 2 * 128 * 128 * 9 * 64 * 1024, 3, 128),
@@ -50,7 +51,8 @@ def load(d):
 
 
 def select(disp, sub, grid, gy, skip=0):
-    sel = [disp[k] for k in sorted(disp, key=int) if sub in disp[k]["name"] and disp[k]["grid"] == grid
+    subs = (sub,) if isinstance(sub, str) else sub
+    sel = [disp[k] for k in sorted(disp, key=int) if any(s in disp[k]["name"] for s in subs) and disp[k]["grid"] == grid
            and disp[k]["gy"] == gy and disp[k]["ns"] and disp[k]["c"]]
     return sel[skip:]
 
