@@ -165,7 +165,11 @@ template <typename TA>
 __global__ __launch_bounds__(INPP_NT) void inpp_bwd_reduce_kernel(const TA* __restrict__ g, const TA* __restrict__ h,
                                                                   const float4* __restrict__ nst, float2* __restrict__ part,
                                                                   int HW, int C) {
-  __shared__ float2 red[INPP_NT * 4];
+  // sum g in float64 from the first add on: the alpha gradient is gamma * mhat * sum g, and mhat -- a channel mean in
+  // units of the spread of the channel means -- reaches 10 and more, so the float32 rounding of a sequential 512-term
+  // sum showed as 13 ulp of d alpha (tests/test_gpu_kernels_aux.py test_inpp_backward); 4 float64 adds per 32 B loaded
+  __shared__ double redg[INPP_NT * 4];
+  __shared__ float redx[INPP_NT * 4];
   const int b = blockIdx.y, grp = blockIdx.x, ngrp = gridDim.x;
   const int C4 = C / 4, PL = INPP_NT / C4, tid = threadIdx.x;
   const int c4 = tid % C4, pl = tid / C4;
@@ -177,7 +181,8 @@ __global__ __launch_bounds__(INPP_NT) void inpp_bwd_reduce_kernel(const TA* __re
     mu = make_float4(n0.x, n1.x, n2.x, n3.x);
     rs = make_float4(n0.y, n1.y, n2.y, n3.y);
   }
-  float sg[4] = {0.f, 0.f, 0.f, 0.f}, sx[4] = {0.f, 0.f, 0.f, 0.f};
+  double sg[4] = {0.0, 0.0, 0.0, 0.0};
+  float sx[4] = {0.f, 0.f, 0.f, 0.f};
   const int npp = INPP_GRP / PL;   // pixels per thread: 8 (C = 64) .. 64 (C = 512), a multiple of 4
   for (int j = 0; j < npp; j += 4) {
     float4 gv[4], hv[4];
@@ -197,16 +202,18 @@ __global__ __launch_bounds__(INPP_NT) void inpp_bwd_reduce_kernel(const TA* __re
     }
   }
 #pragma unroll
-  for (int k = 0; k < 4; ++k) red[(pl * C4 + c4) * 4 + k] = make_float2(sg[k], sx[k]);
+  for (int k = 0; k < 4; ++k) {
+    redg[(pl * C4 + c4) * 4 + k] = sg[k];
+    redx[(pl * C4 + c4) * 4 + k] = sx[k];
+  }
   __syncthreads();
   for (int i = tid; i < C; i += INPP_NT) {
-    float a0 = 0.f, a1 = 0.f;
+    double a0 = 0.0, a1 = 0.0;
     for (int k = 0; k < PL; ++k) {
-      const float2 v = red[(k * C4 + i / 4) * 4 + (i & 3)];
-      a0 += v.x;
-      a1 += v.y;
+      a0 += redg[(k * C4 + i / 4) * 4 + (i & 3)];
+      a1 += (double)redx[(k * C4 + i / 4) * 4 + (i & 3)];
     }
-    part[((size_t)b * ngrp + grp) * C + i] = make_float2(a0, a1);
+    part[((size_t)b * ngrp + grp) * C + i] = make_float2((float)a0, (float)a1);
   }
 }
 
@@ -661,6 +668,7 @@ static hipError_t sum_rows(const float* part, int K, int n, int stride, float* o
 #define SDP_H16(p) reinterpret_cast<const __bf16*>(p)
 #define SDP_H16W(p) reinterpret_cast<__bf16*>(p)
 hipError_t unpool(const float* dout, float* dst, int B, int H, int W, int C, hipStream_t st, bool h16) {
+  if ((H & 1) || (W & 1) || (C & 3)) return hipErrorInvalidValue;   // 2x2 blocks of 4-channel (16-B / 8-B) groups
   const size_t n4 = (size_t)B * H * W * C / 4;
   if (h16) hipLaunchKernelGGL(unpool_kernel<__bf16>, dim3(grid_for(n4)), dim3(256), 0, st, SDP_H16(dout), SDP_H16W(dst), H, W, C, n4);
   else hipLaunchKernelGGL(unpool_kernel<float>, dim3(grid_for(n4)), dim3(256), 0, st, dout, dst, H, W, C, n4);
@@ -688,6 +696,8 @@ hipError_t maxpool5_backward(const uint8_t* idx, const float* dp, const float* r
 }
 
 hipError_t upsample_backward(const float* g, float* dlow, int B, int H, int W, int C, int accumulate, hipStream_t st, bool h16) {
+  // g is the 2x upsampling of dlow; a 1-pixel-high or -wide dlow has scale 0, which the gather's row range divides by
+  if ((H & 1) || (W & 1) || H < 4 || W < 4 || (C & 3)) return hipErrorInvalidValue;
   const size_t n4 = (size_t)B * (H / 2) * (W / 2) * C / 4;
   if (h16)
     hipLaunchKernelGGL(upsample_bwd_kernel<__bf16>, dim3(grid_for(n4)), dim3(256), 0, st, SDP_H16(g), SDP_H16W(dlow), H, W, C,
@@ -698,6 +708,7 @@ hipError_t upsample_backward(const float* g, float* dlow, int B, int H, int W, i
 }
 
 hipError_t elu_backward_post(const float* dy, const float* y, const float* res, float* dst, size_t n, hipStream_t st, bool h16) {
+  if (n & 3) return hipErrorInvalidValue;   // 4-element groups: a tail would be left unwritten
   if (h16)
     hipLaunchKernelGGL(elu_bwd_post_kernel<__bf16>, dim3(grid_for(n / 4)), dim3(256), 0, st, SDP_H16(dy), SDP_H16(y), SDP_H16(res),
                        SDP_H16W(dst), n / 4);
@@ -707,6 +718,7 @@ hipError_t elu_backward_post(const float* dy, const float* y, const float* res, 
 }
 
 hipError_t add_tensors(const float* a, const float* b, float* dst, size_t n, hipStream_t st, bool h16) {
+  if (n & 3) return hipErrorInvalidValue;
   if (h16)
     hipLaunchKernelGGL(add_kernel<__bf16>, dim3(grid_for(n / 4)), dim3(256), 0, st, SDP_H16(a), SDP_H16(b), SDP_H16W(dst), n / 4);
   else

@@ -3,7 +3,7 @@
 The shared library is a build artefact (git-ignored), so a fresh checkout has none. ``ensure_built()``
 compiles it with the csrc Makefile when it is missing or when the sources changed since it was
 built, and raises with the compiler's output if that fails. "Changed" is decided by a content
-hash of every csrc file and include/sdp.h, written next to the library as ``libsdp.so.stamp``
+hash of every csrc file and the include/ headers, written next to the library as ``libsdp.so.stamp``
 (mtimes are not trusted: a tree copied to another machine may carry arbitrary ones -- so a
 rebuild is ``make -B``, which recompiles every object whatever its mtime; ``write_stamp()`` marks
 a library built by hand with ``make`` in csrc/ as current, for the edit-build loop).
@@ -23,6 +23,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 PKG_DIR = os.path.dirname(_HERE)
 CSRC = os.path.join(PKG_DIR, "csrc")
 HEADER = os.path.join(os.path.dirname(PKG_DIR), "include", "sdp.h")
+KERNELS_HEADER = os.path.join(os.path.dirname(PKG_DIR), "include", "sdp_kernels.h")   # the sdpk_* test entries
 LIB_PATH = os.environ.get("SDP_LIB", os.path.join(_HERE, "_lib", "libsdp.so"))
 STAMP = LIB_PATH + ".stamp"
 
@@ -34,8 +35,9 @@ def source_hash() -> str:
         h.update(f.encode())
         with open(os.path.join(CSRC, f), "rb") as fh:
             h.update(fh.read())
-    with open(HEADER, "rb") as fh:
-        h.update(fh.read())
+    for hdr in (HEADER, KERNELS_HEADER):
+        with open(hdr, "rb") as fh:
+            h.update(fh.read())
     return h.hexdigest()
 
 
