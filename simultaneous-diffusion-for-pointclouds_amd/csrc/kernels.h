@@ -5,8 +5,7 @@
 
 namespace sdp {
 
-// OPEN: a non-pooled zero-padded 3x3 (circular = 0, pool = 0, s2 = 0) is admitted but computed
-// with clamped borders -- only the pooled and 4x4 stride-2 kernels are built with zero padding.  No plan launches it.
+// launches a row of conv_inst.hip's table or fails with *why (zero padding: the pooled and 4x4 stride-2 3x3 only)
 hipError_t conv_mfma(int mode, ConvArgs a, int ks, bool pool, hipStream_t st, const char** why);
 // h16: bf16 output (the training tape; bf16 mode)
 hipError_t begin_conv(const float* x, const float* w, const float* bias, float* out, float* stats, int B, int H, int W,

@@ -424,7 +424,8 @@ const char* sdp_last_error(void) { return g_err.c_str(); }
 int sdp_net_create(const sdp_net_desc* desc, sdp_net** out) {
   if (!desc || !out) return fail("sdp_net_create: null argument");
   if (desc->ngf != 128 || desc->channels != 2) return fail("sdp_net_create: only ngf=128, channels=2 are built");
-  if (desc->H % 8 || desc->W % 128) return fail("sdp_net_create: H must be a multiple of 8 and W of 128");
+  // H % 64: every sub-grid of the plan, down to the dilation-4 one at half resolution, tiles into 8 x 16
+  if (desc->H % 64 || desc->W % 128) return fail("sdp_net_create: H must be a multiple of 64 and W of 128");
   if (desc->precision < 0 || desc->precision > 2) return fail("sdp_net_create: bad precision");
   sdp_net* n = new sdp_net();
   n->d = *desc;

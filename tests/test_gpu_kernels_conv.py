@@ -51,7 +51,7 @@ branch) and every tile is a corner; where 2 x 2 tiles do give a multiple of 8 (p
 sub-grid is 1 x 3 tiles instead; at dilation 4 every grid is a multiple of 16 and the branch cannot be taken.
 (b) B = 4 on 2 x 3 tiles (dilation 4: B = 3 on 1 x 3) -- conv_strip_w stops at 1 because 3 is odd, there are edge
 and interior columns, the grid is a multiple of 8; F7 / F8 also on 2 x 6 tiles (strip width 2 of 6 columns), and
-the 16-wide data gradients only there: conv_dgrad checks every sub-grid against its 32-wide fallback tiles, so it
+the 16-wide data gradients only there: conv_dgrad asks for a sub-grid 32 n wide, as the weight gradient does, so it
 admits 16-wide tiles in pairs only (which is also why the training plan rejects W = 128 and 384).  Real
 operands run on (a) only.  Weight gradient: (b) has at least 3 x 3 tiles of the kernel's own tile shape, so interior
 tiles (their own load path in wgrad.hip) beside edge and corner ones -- dilation 4: a third shape, B = 1 on 3 x 3; (a)
@@ -62,12 +62,15 @@ table that every weight-gradient kernel class has a case with an interior tile a
 workgroup.  The forward and data-gradient (b) shapes have edge and corner tiles and interior COLUMNS only (2 tile
 rows: those kernels have one load path, wrap or clamp, for every tile).
 
-Not covered, on purpose: instantiations that no admitted net shape reaches (the 32- and 64-wide forward and data-
-gradient tiles of the bf16 modes, conv_launch_half / dgrad_launch_half, the non-paired <1,16,3> forward, nj2<8> in
-fp32x3, pooled kernels with the prologue the plans never give them, wgrad OCC 2 <64,1> and <32,3>).  Known hole, not
-closed here: conv_mfma admits a NON-pooled zero-padded 3x3 (circular = 0, pool = 0, s2 = 0) although only the pooled
-and 4x4 stride-2 kernels are built with zero padding -- the others clamp at the border.  No plan launches it, and
-conv.hip is one of the five files whose hash keys the committed traffic and clock records.
+Not covered, on purpose: the weight-gradient instantiations that no admitted net shape reaches (wgrad OCC 2 <64,1>
+and <32,3>).  Every forward and data-gradient kernel that is built is a row of conv_inst.hip's table, and every row is
+one of the classes F1 - F10 / D1 - D6 above.
+
+Rejected (the REJECTED table: a non-zero return, the condition in sdp_last_error(), the output untouched): what used
+to reach kernels outside those classes, or no fitting kernel at all.  A NON-pooled zero-padded 3x3 (circular = 0,
+pool = 0, s2 = 0; only the pooled and 4x4 stride-2 kernels are built with zero padding, the others clamp at the
+border); in the bf16 modes a non-pooled 3x3, and any circular 3x3 data gradient, whose sub-grid does not tile into
+8 x 16; a pooled 3x3 without a prologue; a pooled 1x1 with a prologue or in fp32; a non-pooled 1x1 with a prologue.
 """
 import functools
 
@@ -170,7 +173,7 @@ def _dgrad(cls, modes, tr, tc, cin, cout, opts, d=1, **kw):
     for oname, o in opts.items():
         shapes = _shapes(tr, tc, d)
         if tc == 16:
-            # conv_dgrad checks the sub-grid against its 32-wide fallback tiles, so 16-wide tiles come in pairs: (b) has
+            # conv_dgrad asks for a sub-grid 32 n wide (as the weight gradient), so 16-wide tiles come in pairs: (b) has
             # six tile columns (strip width 2), (a) 2 x 2 tiles also under a dilation (no grid off a multiple of 8 then)
             shapes = [("a", 1, 2 * tr * d, 2 * tc * d), ("b", 4 if d < 4 else 3, (2 if d == 1 else 1) * tr * d, 6 * tc * d)]
         for tag, B, H, W in shapes:
@@ -318,9 +321,10 @@ def _new(c, B, H, W, C):
     return torch.full((B, H, W, C), float("nan"), dtype=torch.bfloat16 if c.io16 else torch.float32, device=DEV)
 
 
-def run_case(c: Case, mode, o=None):
+def run_case(c: Case, mode, o=None, outputs=None):
     """Launch case c in mode `mode` (on the operands o, else the case's own); returns {name: NCHW float64 CPU
-    tensor} (+ 'stats': [B][T][C][2], 'cnt')."""
+    tensor} (+ 'stats': [B][T][C][2], 'cnt').  outputs: a list that receives the NaN-filled forward / data-gradient
+    output tensor before the launch (for the callers that expect the launch to be refused)."""
     o = _operands(c) if o is None else o
     L, m = KL.lib(), KR.MODES[mode]
     f32 = lambda t: t.to(torch.float32).contiguous().to(DEV)
@@ -358,6 +362,8 @@ def run_case(c: Case, mode, o=None):
     pk = KL.pack_weights(w, m, packing)
     Ho, Wo = c.out_hw()
     out = _new(c, c.B, Ho, Wo, cout)
+    if outputs is not None:
+        outputs.append(out)
     keep += [x, ss, pk, out]
     a.in_, a.out, a.pro_ss = x.data_ptr(), out.data_ptr(), ss.data_ptr()
     if packing == KL.PACK_FRAG:
@@ -463,6 +469,34 @@ def _launch_error(c: Case, mode, needle):
     with pytest.raises(KL.KernelError) as e:
         run_case(c, mode)
     assert needle in str(e.value), str(e.value)
+
+
+# Combinations no kernel is built for (conv_inst.hip's table): the launch is refused, with the unmet condition in
+# sdp_last_error(), and nothing is written.  Smallest shapes that pass every earlier check; buffers at full size and
+# valid packed weights, so a launch that wrongly went ahead would stay inside them.
+REJECTED = (
+    # a non-pooled zero-padded 3x3: the non-pooled kernels clamp at the border
+    (Case("rej-fwd-zp", "fwd", 1, 16, 32, 128, 128, circular=False), ALL3, "needs circular padding"),
+    # tiles 4 x 32 but not 8 x 16: ran on the retired 32-wide tiles of the bf16 modes (data gradient: 64-wide)
+    (Case("rej-fwd-4x32", "fwd", 1, 4, 32, 256, 256), B16, "8 x 16 pixel tile"),
+    (Case("rej-dgrad-4x64", "dgrad", 1, 4, 64, 256, 256), B16, "8 x 16 tiles of a circular 3x3"),
+    # prologues the pooled and 1x1 kernels are not built with
+    (Case("rej-pool3-none", "fwd", 1, 4, 64, 128, 256, circular=False, pool=True, pro=NONE), ALL3, "pooled 3x3 needs an ELU prologue"),
+    (Case("rej-pool1-elu", "fwd", 1, 4, 64, 128, 256, ks=1, circular=False, pool=True, pro=ELU), B16, "pooled 1x1 needs"),
+    (Case("rej-pool1-fp32", "fwd", 1, 4, 64, 128, 256, ks=1, circular=False, pool=True), ("fp32",), "pooled 1x1 needs"),
+    (Case("rej-1x1-elu", "fwd", 1, 2, 64, 128, 256, ks=1, circular=False, pro=ELU), ALL3, "non-pooled 1x1 takes no prologue"),
+)
+
+
+@pytest.mark.parametrize("c,mode,needle", [pytest.param(c, m, needle, id=f"{c.name}-{m}")
+                                           for c, modes, needle in REJECTED for m in modes])
+def test_unbuilt_combinations_are_rejected(c, mode, needle):
+    outputs = []
+    with pytest.raises(KL.KernelError) as e:      # raised on a non-zero return, with sdp_last_error()
+        run_case(c, mode, outputs=outputs)
+    assert needle in str(e.value), str(e.value)
+    torch.cuda.synchronize()
+    assert len(outputs) == 1 and torch.isnan(outputs[0]).all(), f"{c.name} {mode}: the output was written"
 
 
 def test_launchers_reject_what_their_kernels_cannot_index():

@@ -44,6 +44,16 @@ def test_errors_are_reported_not_crashing():
     assert b"ngf" in L.sdp_last_error()
 
 
+def test_net_create_rejects_a_height_off_the_tile_grid():
+    """H = 32: the dilation-4 sub-grid at half resolution is 4 rows, less than one 8 x 16 tile."""
+    from sdp import _lib
+    L = _lib.lib()
+    d = _lib.NetDesc(128, 2, 32, 1024, 232, 1)
+    h = _lib.P()
+    assert L.sdp_net_create(_lib.C.byref(d), _lib.C.byref(h)) != 0
+    assert b"64" in L.sdp_last_error()
+
+
 def test_one_hip_runtime_in_process():
     """libsdp must bind to torch's libamdhip64 instance (shared SONAME), never a second copy."""
     from sdp import _lib
