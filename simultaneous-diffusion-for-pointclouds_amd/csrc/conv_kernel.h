@@ -67,6 +67,10 @@ namespace sdp {
 #endif                // per fp32x3 B=4 launch in the profiled pass; the line step could not tell them apart (374.3-375.6
                       // vs 374.8-375.5 image-steps/s, profiles/experiments/r07_pool4x4_ring_ab.log)
 
+#ifndef SDP_ROWS      // the forward 8 x 16 tiles' A fragments as a ring of patch rows, taps kw-major (ROWS below);
+#define SDP_ROWS 1    // 0 (build-time A/B) = the per-tap fragments ca / cb of every other tile shape
+#endif
+
 #ifdef SDP_TIMING   // tools/conv_bench: per-workgroup phase clocks of wave 0 into a.dbg
 #define SDP_T(i) do { if (tid == 0) tclk[i] = __builtin_amdgcn_s_memtime(); } while (0)
 #else
@@ -148,6 +152,64 @@ constexpr int s2_pos(int phase, int t) {
   return ((rho ? 0 : 1) + (t >> 1)) * 3 + (gamma ? 0 : 1) + (t & 1);
 }
 
+// The 8 x 16 tiles' 3x3 tap schedule (conv_mfma_kernel ROWS) runs its taps kw-major -- (0,kw), (1,kw), (2,kw) for
+// kw = 0, 1, 2 -- so that consecutive taps share 7 of their 8 patch rows: a chunk reads each of the 10 patch rows
+// once per kw (30 fragments, hi and lo) instead of 8 rows per tap (72).  rows_pos: patch position 3 kh + kw of the tap
+// at position o of that order.  Tap kh multiplies patch row mb + kh for the 16-px group mb; the blocks (s, nj, i)
+// use group mb first in block mb (mb < 4) or 4 + mb and last in block 4 + mb or 8 + mb.
+// The fragments sit in a ring of 9 slots (72 VGPRs in fp32x3; ca / cb were 64), slot = (row + kw) % 9: row 9 takes
+// over the slot of its own kw's row 0 (done after tap kh = 0), and row r of the next kw the slot of row r + 1 (row 0
+// once tap kh = 1 is done with row 1, rows 1 .. 6 under tap kh = 2 as its groups retire, rows 7 and 8 under the next
+// tap's first blocks) -- one read per block, 10 or more blocks ahead of its first use, never a burst.  The first kw
+// of a chunk cannot be read ahead (its patch buffer completes at the chunk barrier): rows 0 .. 3 are read up
+// front, rows 4 .. 7 under blocks 0 .. 7 (first use: block 8), row 8 under blocks 8, 9.
+// rows_read: the read dealt to block blk of the tap at position o as a filler (-1: none), coded 4 * patch row +
+// 2 * (lo part) + (the row belongs to the NEXT kw).
+constexpr int ROWS_SLOTS = 9;
+constexpr int rows_pos(int o) { return (o % 3) * 3 + o / 3; }
+constexpr int rows_slot(int kw, int row) { return (row + kw) % ROWS_SLOTS; }
+constexpr int rows_read(int o, int blk) {
+  const int kh = o % 3, kw = o / 3, lo = blk & 1;
+  if (kh == 0) {
+    if (kw == 0 && blk < 10) return 4 * (4 + blk / 2) + 2 * lo;
+    if (kw > 0 && blk < 4) return 4 * (7 + blk / 2) + 2 * lo;
+    if (blk == 10 || blk == 11) return 4 * 9 + 2 * lo;
+  } else if (kh == 1) {
+    if (kw < 2 && (blk == 8 || blk == 10)) return 4 * 0 + 2 * (blk == 10 ? 1 : 0) + 1;
+  } else {
+    if (kw < 2 && blk >= 4) return 4 * (1 + (blk - 4) / 2) + 2 * lo + 1;
+  }
+  return -1;
+}
+// the plan reads every (kw, row, part) once, after the last use of the row that held its slot has issued and before
+// its own first use (time = 16 * tap position + block; a filler follows its block's MFMAs)
+constexpr bool rows_plan_ok() {
+  for (int kw = 0; kw < 3; ++kw)
+    for (int row = 0; row < 10; ++row)
+      for (int lo = 0; lo < 2; ++lo) {
+        int n = (kw == 0 && row < 4) ? 1 : 0, at = -1;
+        for (int o = 0; o < 9; ++o)
+          for (int blk = 0; blk < 16; ++blk) {
+            const int c = rows_read(o, blk);
+            if (c >= 0 && o / 3 + (c & 1) == kw && c / 4 == row && ((c >> 1) & 1) == lo) {
+              ++n;
+              at = 16 * o + blk;
+            }
+          }
+        if (n != 1) return false;
+        const int kh0 = row > 7 ? row - 7 : 0, mb0 = row - kh0;
+        if (at >= 16 * (3 * kw + kh0) + (mb0 < 4 ? mb0 : 4 + mb0)) return false;
+        // the slot's previous row: row 0 of this kw (row 9), else row + 1 of the previous kw
+        const int pkw = row == 9 ? kw : kw - 1, prow = row == 9 ? 0 : row + 1;
+        if (pkw < 0) continue;
+        if (rows_slot(pkw, prow) != rows_slot(kw, row)) return false;
+        const int kh1 = prow < 2 ? prow : 2, mb1 = prow - kh1;
+        if (at < 16 * (3 * pkw + kh1) + (mb1 < 4 ? 4 + mb1 : 8 + mb1)) return false;
+      }
+  return true;
+}
+static_assert(rows_plan_ok(), "A-fragment ring: a row is read once, between its slot's last use and its own first");
+
 // SH: MFMA shape of the bf16 modes -- 32 = v_mfma_f32_32x32x16_bf16 (wave tile = 4 x 2 fragments
 // of 32 px x 32 Cout, two 16-deep k steps per 32-channel chunk), 16 = v_mfma_f32_16x16x32_bf16
 // (8 x 4 fragments of 16 px x 16 Cout, one 32-deep k step per chunk).  Same cycles per FLOP; the
@@ -193,6 +255,8 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
   constexpr bool TRANS = TRN && SH == 16 && !POOL;
   constexpr int NU = T::NU;
   constexpr int XT = NT >= 4 ? 4 : NT;            // taps that carry the transform of the next chunk
+  // the forward 3x3 on 8 x 16 tiles: kw-major taps on a ring of patch-row A fragments (rows_pos, rows_read)
+  constexpr bool ROWS = SDP_ROWS && SH == 16 && !S2 && NT == 9 && TC == 16 && NJ == 2 && !TRANS;
   __shared__ __attribute__((aligned(16))) char lds[T::LDS_BYTES];
   char* const raw = lds + 2 * T::PATCH_BYTES;
 
@@ -338,9 +402,12 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
   const int my_cv = tid & (T::UPP - 1);            // every unit of a thread has cv == tid % UPP
   // (scale, shift) of this thread's CPU channels, double-buffered by chunk parity: chunk c's rows live
   // in ssv[c & 1][..] (the transform of chunk c writes patch buffer c & 1 too); float4 k = channels 2k, 2k+1
+  // (PELU == false serves PRO_NONE only -- the enum has no affine-only prologue -- whose table is the identity:
+  // those instantiations load no rows and skip the fmaf)
   float4 ssv[2][PPU];
   auto load_ss = [&](auto buf, int chunk) __attribute__((always_inline)) {
     constexpr int SB = decltype(buf)::value;
+    if constexpr (!PELU) return;
     static_for<0, PPU>([&](auto kc) { ssv[SB][kc] = ld4(ssb + (chunk * 32 + my_cv * CPU) * 2 + 4 * decltype(kc)::value); });
   };
 
@@ -420,9 +487,10 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
       float x8[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        const float4 sv = ssv[PB][e >> 1];
-        x8[e] = fmaf(x8[e], (e & 1) ? sv.z : sv.x, (e & 1) ? sv.w : sv.y);
-        if constexpr (PELU) x8[e] = elu_max(x8[e]);
+        if constexpr (PELU) {
+          const float4 sv = ssv[PB][e >> 1];
+          x8[e] = elu_max(fmaf(x8[e], (e & 1) ? sv.z : sv.x, (e & 1) ? sv.w : sv.y));
+        }
         if constexpr (ZP) {
           if (!((uvalid >> k) & 1u)) x8[e] = 0.f;
         }
@@ -431,12 +499,12 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
           make_uint4(pack_bf2(x8[0], x8[1]), pack_bf2(x8[2], x8[3]), pack_bf2(x8[4], x8[5]), pack_bf2(x8[6], x8[7]));
       return;
     }
-    const float4 ssv0 = ssv[PB][0], ssv1 = ssv[PB][1];
-    v.x = fmaf(v.x, ssv0.x, ssv0.y);
-    v.y = fmaf(v.y, ssv0.z, ssv0.w);
-    v.z = fmaf(v.z, ssv1.x, ssv1.y);
-    v.w = fmaf(v.w, ssv1.z, ssv1.w);
     if constexpr (PELU) {
+      const float4 ssv0 = ssv[PB][0], ssv1 = ssv[PB][1];
+      v.x = fmaf(v.x, ssv0.x, ssv0.y);
+      v.y = fmaf(v.y, ssv0.z, ssv0.w);
+      v.z = fmaf(v.z, ssv1.x, ssv1.y);
+      v.w = fmaf(v.w, ssv1.z, ssv1.w);
       v.x = elu_max(v.x); v.y = elu_max(v.y); v.z = elu_max(v.z); v.w = elu_max(v.w);
     }
     if constexpr (ZP) {   // zero padding (ConvMeanPool, layers.py:291-313, and its data gradient)
@@ -474,12 +542,10 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
       x0 = h ? v4.z : v4.x;
       x1 = h ? v4.w : v4.y;
     }
-    const float4 sv = ssv[PB][h];
-    x0 = fmaf(x0, sv.x, sv.y);
-    x1 = fmaf(x1, sv.z, sv.w);
     if constexpr (PELU) {
-      x0 = elu_max(x0);
-      x1 = elu_max(x1);
+      const float4 sv = ssv[PB][h];
+      x0 = elu_max(fmaf(x0, sv.x, sv.y));
+      x1 = elu_max(fmaf(x1, sv.z, sv.w));
     }
     if constexpr (ZP) {
       const bool ok = (uvalid >> k) & 1u;
@@ -503,7 +569,7 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
   SDP_T(1);
   // ---- prologue: chunk 0 staged + transformed, chunk 1 in flight ----
   load_b(std::integral_constant<int, 0>{}, 0, 0);
-  static_for<1, NBUF - 1>([&](auto j) { load_b(j, 0, decltype(j)::value); });
+  static_for<1, NBUF - 1>([&](auto j) { load_b(j, 0, ROWS ? rows_pos(decltype(j)::value) : decltype(j)::value); });
   load_ss(std::integral_constant<int, 0>{}, 0);
   static_for<0, NU>([&](auto k) { load_unit(k, 0); });
   static_for<0, NU>([&](auto k) { xform_unit(k, std::integral_constant<int, 0>{}); });
@@ -672,6 +738,9 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
   //   blocks 2 .. 31         : their transform, 5 stages per 2-channel piece
   //   blocks 30, 31          : the LDS-DMA of those units for the chunk after next (raw slot free)
   // (IO16: 4 pieces per unit; S2: up to two units per tap)
+  // ROWS (the forward 8 x 16 tiles, 16 blocks per tap): the taps run kw-major and the A fragments are the patch rows
+  // of the current kw in a 9-slot ring instead of ca / cb -- 60 reads per chunk (bf16: 30) instead of 144 (72), dealt
+  // by rows_read; the other fillers keep their blocks
   using XP = XformPlan<NU, NT, (MODE == MODE_BF16 && !IO16 && !S2) ? 8 : 5>;
   constexpr int NQ = MODE == MODE_F32X3 ? 8 : 4;   // A reads per half tap
   constexpr int NWL = NJ * (MODE == MODE_F32X3 ? 2 : 1);   // weight loads per tap
@@ -701,10 +770,21 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
     constexpr int P = decltype(parity)::value, PHS = decltype(phase_c)::value;
     const char* pat = lds + P * T::PATCH_BYTES;
     bf16x8 ca[2][4], cb[2][4];   // [hi, lo][i]: half s = 0 / s = 1 of the current tap
+    bf16x8 ar[2][ROWS ? ROWS_SLOTS : 1];   // ROWS: [hi, lo][rows_slot] instead, the patch rows of the current kw
+    // ROWS: patch row `row` at column offset kw -- the fragment of the 16-px group mb = row - kh of tap (kh, kw)
+    auto read_row = [&](auto kw_c, auto row_c, auto lo_c) __attribute__((always_inline)) {
+      return *reinterpret_cast<const bf16x8*>(pat + ((wrow0 + decltype(row_c)::value) * T::PC + decltype(kw_c)::value) * PSTRIDE +
+                                              a_lane_off16 + (decltype(lo_c)::value ? 64 : 0));
+    };
     static_for<0, 4>([&](auto i) {
-      using POS0 = std::integral_constant<int, S2 ? s2_pos(PHS, 0) : 0>;
-      ca[0][i] = read_a1(pat, POS0{}, I0{}, i, I0{});
-      if constexpr (MODE == MODE_F32X3) ca[1][i] = read_a1(pat, POS0{}, I0{}, i, I1{});
+      if constexpr (ROWS) {
+        ar[0][rows_slot(0, i)] = read_row(I0{}, i, I0{});
+        if constexpr (MODE == MODE_F32X3) ar[1][rows_slot(0, i)] = read_row(I0{}, i, I1{});
+      } else {
+        using POS0 = std::integral_constant<int, S2 ? s2_pos(PHS, 0) : 0>;
+        ca[0][i] = read_a1(pat, POS0{}, I0{}, i, I0{});
+        if constexpr (MODE == MODE_F32X3) ca[1][i] = read_a1(pat, POS0{}, I0{}, i, I1{});
+      }
     });
     load_ss(std::integral_constant<int, P>{}, chunk_cc(min(chunk + 2, nchunks - 1)));   // buffer P: chunk-1's, free
     static_for<0, NT>([&](auto tap_c) {
@@ -716,7 +796,8 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
       constexpr int U0 = XP::first(tap), UN = XP::count(tap), Q = COPY ? UN : UN * PPU * XP::NSTG;
       constexpr int UNA = UN > 0 ? UN : 1;
       const int wchunk = tap + DIST < NT ? chunk : min(chunk + 1, nchunks - 1);
-      constexpr int wtap = tap + DIST < NT ? tap + DIST : tap + DIST - NT;
+      constexpr int wnext = tap + DIST < NT ? tap + DIST : tap + DIST - NT;
+      constexpr int wtap = ROWS ? rows_pos(wnext) : wnext;   // (ROWS: `tap` is the position in the kw-major order)
       float4 xr[UNA];                                  // raw values of this tap's units
       float py0[PPU * UNA], py1[PPU * UNA], pe0[PPU * UNA], pe1[PPU * UNA];
       uint32_t phi[PPU * UNA], plo[PPU * UNA];
@@ -745,13 +826,18 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
         };
         if constexpr (XP::NSTG == 8) {   // bf16: the same arithmetic one value at a time
           const float4 v = xr[j];
-          const float4 sv = ssv[PB][h];
           if constexpr (st == 0) {
-            py0[pc] = fmaf(h ? v.z : v.x, sv.x, sv.y);
-            if constexpr (PELU) pe0[pc] = fminf(py0[pc], 0.f);
+            py0[pc] = h ? v.z : v.x;
+            if constexpr (PELU) {
+              py0[pc] = fmaf(py0[pc], ssv[PB][h].x, ssv[PB][h].y);
+              pe0[pc] = fminf(py0[pc], 0.f);
+            }
           } else if constexpr (st == 1) {
-            py1[pc] = fmaf(h ? v.w : v.y, sv.z, sv.w);
-            if constexpr (PELU) pe1[pc] = fminf(py1[pc], 0.f);
+            py1[pc] = h ? v.w : v.y;
+            if constexpr (PELU) {
+              py1[pc] = fmaf(py1[pc], ssv[PB][h].z, ssv[PB][h].w);
+              pe1[pc] = fminf(py1[pc], 0.f);
+            }
           } else if constexpr (st == 2) {
             if constexpr (PELU) pe0[pc] = __expf(pe0[pc]);
           } else if constexpr (st == 3) {
@@ -777,10 +863,12 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
         if constexpr (st == 0) {
           float r0, r1;
           raw2(r0, r1);
-          const float4 sv = ssv[PB][h];
-          py0[pc] = fmaf(r0, sv.x, sv.y);
-          py1[pc] = fmaf(r1, sv.z, sv.w);
+          py0[pc] = r0;
+          py1[pc] = r1;
           if constexpr (PELU) {
+            const float4 sv = ssv[PB][h];
+            py0[pc] = fmaf(r0, sv.x, sv.y);
+            py1[pc] = fmaf(r1, sv.z, sv.w);
             pe0[pc] = fminf(py0[pc], 0.f);
             pe1[pc] = fminf(py1[pc], 0.f);
           }
@@ -828,17 +916,23 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
           const uint4 h4 = bq[CUR][nj >> 1][2 * (nj & 1)], l4 = bq[CUR][nj >> 1][2 * (nj & 1) + 1];
           const bf16x8 bhi = *reinterpret_cast<const bf16x8*>(&h4);
           const bf16x8 blo = *reinterpret_cast<const bf16x8*>(&l4);
-          const bf16x8 ahi = s == 0 ? ca[0][i] : cb[0][i];
+          // (ROWS: tap position `tap` is (kh, kw) = (tap % 3, tap / 3); group mb reads patch row mb + kh)
+          auto afrag = [&](auto lo_c) __attribute__((always_inline)) {
+            constexpr int lo = decltype(lo_c)::value;
+            if constexpr (ROWS) return ar[lo][rows_slot(tap / 3, mb + tap % 3)];
+            else return s == 0 ? ca[lo][i] : cb[lo][i];
+          };
+          const bf16x8 ahi = afrag(I0{});
           if constexpr (TRANS) {   // D = W x X: rows = Cout, columns = pixels (same fragment registers)
             if constexpr (MODE == MODE_F32X3) {
-              const bf16x8 alo = s == 0 ? ca[1][i] : cb[1][i];
+              const bf16x8 alo = afrag(I1{});
               acc4[mb][nj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bhi, alo, acc4[mb][nj], 0, 0, 0);
               acc4[mb][nj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(blo, ahi, acc4[mb][nj], 0, 0, 0);
             }
             acc4[mb][nj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bhi, ahi, acc4[mb][nj], 0, 0, 0);
           } else {
             if constexpr (MODE == MODE_F32X3) {
-              const bf16x8 alo = s == 0 ? ca[1][i] : cb[1][i];
+              const bf16x8 alo = afrag(I1{});
               acc4[mb][nj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(alo, bhi, acc4[mb][nj], 0, 0, 0);
               acc4[mb][nj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahi, blo, acc4[mb][nj], 0, 0, 0);
             }
@@ -846,13 +940,18 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
           }
         }
         // ---- fillers for later taps
-        if constexpr (blk < NQ) {   // this tap's half-1 fragments (used from block NBLK / 2)
+        if constexpr (ROWS) {   // one read of the row plan (bf16: the hi parts only)
+          constexpr int c = rows_read(tap, blk);
+          if constexpr (c >= 0 && (MODE == MODE_F32X3 || !(c & 2)))
+            ar[(c >> 1) & 1][rows_slot(tap / 3 + (c & 1), c / 4)] = read_row(std::integral_constant<int, tap / 3 + (c & 1)>{}, std::integral_constant<int, c / 4>{},
+                                               std::integral_constant<int, (c >> 1) & 1>{});
+        } else if constexpr (blk < NQ) {   // this tap's half-1 fragments (used from block NBLK / 2)
           constexpr int q = blk, ii = MODE == MODE_F32X3 ? (q >> 1) : q, lo = MODE == MODE_F32X3 ? (q & 1) : 0;
           cb[lo][ii] = read_a1(pat, POS{}, I1{}, std::integral_constant<int, ii>{}, std::integral_constant<int, lo>{});
         }
         if constexpr ((blk & 1) && (blk >> 1) < NWL)   // tap + 2's weights
           load_b1(std::integral_constant<int, NXT>{}, std::integral_constant<int, (blk >> 1)>{}, wchunk, wtap);
-        if constexpr (tap + 1 < NT && blk >= NBLK / 2 && blk < NBLK / 2 + NQ) {   // tap + 1's half-0 fragments
+        if constexpr (!ROWS && tap + 1 < NT && blk >= NBLK / 2 && blk < NBLK / 2 + NQ) {   // tap + 1's half-0 fragments
           constexpr int q = blk - NBLK / 2, ii = MODE == MODE_F32X3 ? (q >> 1) : q, lo = MODE == MODE_F32X3 ? (q & 1) : 0;
           ca[lo][ii] = read_a1(pat, POSN{}, I0{}, std::integral_constant<int, ii>{},
                                std::integral_constant<int, lo>{});
