@@ -107,6 +107,40 @@ int sdpk_inpp_backward(const void* g, const void* h, const float* nst, const flo
                        int HW, int C, float* part, float* coef, float* ppart, float* dalpha, float* dgamma, float* dbeta,
                        const void* r1, const void* r2, void* out, int h16, void* stream);
 
+/* ---- the head and the tail of the score net (aux.hip, train_aux.hip).  mode: enum sdp_precision */
+/* x: [B][2][H][W] image (NCHW float32); w: [128][4][3][3]; bias: [128]; out: [B][H][W][128] (bf16 elements when
+ * h16); stats: [B][H*W/64][128][2] (mean, M2) of groups of 64 pixels.  W a multiple of 128; h16 in bf16 mode only */
+int sdpk_begin_conv(const float* x, const float* w, const float* bias, void* out, float* stats, int B, int H, int W,
+                    int mode, int h16, void* stream);
+/* the fused Langevin update of sdpk_end_conv: csrc/langevin.h LangevinArgs */
+typedef struct sdpk_langevin {
+  float* x;              /* [B][2][H][W], updated in place                                              */
+  const float* ref;      /* [B][2][H][W]                                                                */
+  const int32_t* mask;   /* [B][2][H][W]                                                                */
+  const float* noise;    /* nullable: Philox4x32-10(seed, offset + i / 4)                               */
+  uint64_t seed, offset;
+  float step_size, noise_scale, grad_ref;
+  int nan_to_num;
+  float* lik_out;        /* nullable                                                                    */
+  uint32_t* absmax_bits; /* nullable: atomicMax of the float bits of |x_new[:, 0]|                      */
+} sdpk_langevin;
+/* in: [B][H][W][Cin] (bf16 elements when h16); ss: [B][Cin][2] (scale, shift); w: [2][Cin][3][3]; bias: [2];
+ * out: [B][2][H][W] = (conv3x3_zero(ELU(in * scale + shift), w) + bias) / sigmas[labels[b]] (nullable with lg);
+ * labels: int64 [B].  Cin = 128; bf16 modes: 16 x 32 tiles, else (and fp32) the direct kernel on 4 x 64 tiles */
+int sdpk_end_conv(const void* in, const float* ss, const float* w, const float* bias, const float* sigmas,
+                  const int64_t* labels, float* out, int B, int H, int W, int Cin, int mode, int h16,
+                  const sdpk_langevin* lg_or_null, void* stream);
+/* dw [128][4][3][3], db [128]: gradients of the begin conv for dy [B][H][W][128] (bf16 elements when h16);
+ * part: sdpk_head_wgrad_part_floats(B, H, W) floats.  H a multiple of 8, W of 64 */
+int sdpk_begin_conv_wgrad(const float* x, const void* dy, float* part, float* dw, float* db, int B, int H, int W, int h16,
+                          void* stream);
+/* dscore [B][2][H][W]; o, ss: the forward's in, ss; g [B][H][W][128] = d loss / d (o * scale + shift) (o, g: bf16
+ * elements when h16); dw [2][128][3][3], db [2]; part as above.  H a multiple of 16, W of 64 */
+int sdpk_end_conv_backward(const float* dscore, const float* sigmas, const int64_t* labels, const float* w, const void* o,
+                           const float* ss, void* g, float* part, float* dw, float* db, int B, int H, int W, int h16,
+                           void* stream);
+size_t sdpk_head_wgrad_part_floats(int B, int H, int W);
+
 #ifdef __cplusplus
 }
 #endif

@@ -158,4 +158,45 @@ int sdpk_inpp_backward(const void* g, const void* h, const float* nst, const flo
               "sdpk_inpp_backward");
 }
 
+int sdpk_begin_conv(const float* x, const float* w, const float* bias, void* out, float* stats, int B, int H, int W,
+                    int mode, int h16, void* stream) {
+  return done(begin_conv(x, w, bias, F(out), stats, B, H, W, S(stream), mode, h16 != 0), "sdpk_begin_conv");
+}
+
+int sdpk_end_conv(const void* in, const float* ss, const float* w, const float* bias, const float* sigmas,
+                  const int64_t* labels, float* out, int B, int H, int W, int Cin, int mode, int h16,
+                  const sdpk_langevin* lg, void* stream) {
+  LangevinArgs la{};
+  if (lg) {
+    la.x = lg->x;
+    la.ref = lg->ref;
+    la.mask = lg->mask;
+    la.noise = lg->noise;
+    la.seed = lg->seed;
+    la.offset = lg->offset;
+    la.step = lg->step_size;
+    la.nscale = lg->noise_scale;
+    la.gref = lg->grad_ref;
+    la.n2n = lg->nan_to_num;
+    la.lik = lg->lik_out;
+    la.absmax = lg->absmax_bits;
+  }
+  return done(end_conv(F(in), ss, w, bias, sigmas, labels, out, B, H, W, Cin, S(stream), lg ? &la : nullptr, mode, h16 != 0),
+              "sdpk_end_conv");
+}
+
+int sdpk_begin_conv_wgrad(const float* x, const void* dy, float* part, float* dw, float* db, int B, int H, int W, int h16,
+                          void* stream) {
+  return done(begin_conv_wgrad(x, F(dy), part, dw, db, B, H, W, S(stream), h16 != 0), "sdpk_begin_conv_wgrad");
+}
+
+int sdpk_end_conv_backward(const float* dscore, const float* sigmas, const int64_t* labels, const float* w, const void* o,
+                           const float* ss, void* g, float* part, float* dw, float* db, int B, int H, int W, int h16,
+                           void* stream) {
+  return done(end_conv_backward(dscore, sigmas, labels, w, F(o), ss, F(g), part, dw, db, B, H, W, S(stream), h16 != 0),
+              "sdpk_end_conv_backward");
+}
+
+size_t sdpk_head_wgrad_part_floats(int B, int H, int W) { return head_wgrad_part_floats(B, H, W); }
+
 }  // extern "C"

@@ -28,6 +28,12 @@ class Wgrad(C.Structure):
                 ("circular", I)]
 
 
+class Langevin(C.Structure):
+    _fields_ = [("x", P), ("ref", P), ("mask", P), ("noise", P), ("seed", C.c_uint64), ("offset", C.c_uint64),
+                ("step_size", Fl), ("noise_scale", Fl), ("grad_ref", Fl), ("nan_to_num", I), ("lik_out", P),
+                ("absmax_bits", P)]
+
+
 SIGS = {
     "sdpk_pack_weights": (I, [P, P, I, I, I, I, I, P, P]),
     "sdpk_conv_mfma": (I, [I, C.POINTER(Conv), I, I, P]),
@@ -44,6 +50,11 @@ SIGS = {
     "sdpk_add_tensors": (I, [P, P, P, SZ, I, P]),
     "sdpk_inpp_finalize": (I, [P, I, I, Fl, I, P, P, P, P, P, P, P]),
     "sdpk_inpp_backward": (I, [P, P, P, P, P, I, I, I, P, P, P, P, P, P, P, P, P, I, P]),
+    "sdpk_begin_conv": (I, [P, P, P, P, P, I, I, I, I, I, P]),
+    "sdpk_end_conv": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, C.POINTER(Langevin), P]),
+    "sdpk_begin_conv_wgrad": (I, [P, P, P, P, P, I, I, I, I, P]),
+    "sdpk_end_conv_backward": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, P]),
+    "sdpk_head_wgrad_part_floats": (SZ, [I, I, I]),
 }
 
 _bound = None

@@ -1,8 +1,9 @@
 """Float64 references, operand generators and gates for the per-kernel parity tests (pure CPU).
 
-The kernels between begin_conv and end_conv are compared one launch at a time (tests/test_gpu_kernels_*.py, through
-the sdpk_* entries of include/sdp_kernels.h) with float64 torch restatements of the same operation.  Tensors are NCHW
-float64 in here; the GPU modules convert to NHWC at the boundary.
+The score net's kernels -- begin_conv and end_conv, their backward kernels and the DSM loss included (the "head"
+section below) -- are compared one launch at a time (tests/test_gpu_kernels_*.py, through the sdpk_* entries of
+include/sdp_kernels.h) with float64 torch restatements of the same operation.  Tensors are NCHW float64 in here; the
+GPU modules convert to NHWC at the boundary.
 
 Two kinds of operands:
 
@@ -485,3 +486,295 @@ def elu_post_gate(dy, y, res, ref, h16=False):
 
 def add_gate(a, b, h16=False):
     return EPS24 * (a.abs() + b.abs()) + (2.0 ** -8 * (a + b).abs() if h16 else 0.0)
+
+
+# ---------------------------------------------------------------------------------------------- head and tail kernels
+# begin_conv (input prep + zero-padded 4 -> 128 conv + statistics), end_conv (IN++ affine + ELU + zero-padded
+# 128 -> 2 conv, / sigmas[labels[b]]), their backward kernels and the DSM loss.  Operands as above, with
+#   begin conv     image x in {0..8}/8 (2x - 1 on the 1/4 lattice); the y-coordinate channel is exact in float32 and
+#                  bf16 when H = 2^k + 1 (step 1/2^k, k <= 7); the x-coordinate channel never is (W is a multiple of
+#                  128), so the forward lattice cases give that input channel zero weights
+#   end conv       the test's OWN table of power-of-two sigmas, picked out of order by the labels: the division is exact
+# K (the reduction length of the gates): 37 begin conv, 9 * 128 + 1 end conv, 18 end data gradient, B * H * W the
+# head weight gradients.  The backward kernels are plain float32 in every mode: the fp32 row of the table.
+SIGMA_ORDER = (2, 0, 3, 1)      # labels of images 0, 1, 2, ...: a different table entry each, out of order
+HEAD_OPS = ("begin", "end", "begin_wgrad", "end_bwd")
+
+
+@dataclasses.dataclass(frozen=True)
+class Head:
+    """One launch of a head / tail kernel.  op: begin | end | begin_wgrad | end_bwd.  h16: the bf16 tape's tensor of the
+    call (begin: out; end: in; begin_wgrad: dy; end_bwd: o and g)."""
+    name: str
+    op: str
+    B: int
+    H: int
+    W: int
+    real: bool = False
+    h16: bool = False
+    sigmas: tuple = (0.5, 1.0, 2.0, 4.0)
+
+    @property
+    def id(self):
+        return self.name
+
+    def labels(self):
+        return [SIGMA_ORDER[b % 4] for b in range(self.B)]
+
+    def K(self, key="out"):
+        if self.op == "begin":
+            return 37
+        if self.op == "end":
+            return 9 * 128 + 1
+        if self.op == "end_bwd" and key == "g":
+            return 18
+        return self.B * self.H * self.W
+
+    def end_case(self):
+        return Case(self.name, "fwd", self.B, self.H, self.W, 128, 2, circular=False, pro=PRO_AFFINE_ELU, bias=True,
+                    real=self.real, io16=self.h16)
+
+    def lattice_bound(self):
+        """Largest partial sum in lattice units; below 2^24 float32 is exact.
+        begin: activations in 1/128 (the y coordinate's step is >= 1/128; H - 1 must be a power of two <= 128),
+        weights in 1/8: 37 terms of <= 128 * 4 units.  end: the conv's own bound (the division by a power of two is
+        exact).  begin_wgrad: B H W terms of 4 * 4 units of 1/16 (image channels and bias).  end_bwd: dscore / sigma
+        in units of 1 / (4 max sigma), <= 4 max / min of them; times 4 weight units over 18 terms (g), times
+        10 activation units over B H W terms (dw)."""
+        n = self.B * self.H * self.W
+        if self.op == "begin":
+            k = self.H - 1
+            return 37 * 128 * 4 if (k & (k - 1)) == 0 and 1 <= k <= 128 else 2 ** 24
+        if self.op == "end":
+            return self.end_case().lattice_bound()
+        if self.op == "begin_wgrad":
+            return n * 4 * 4
+        d = int(4 * max(self.sigmas) / min(self.sigmas))
+        return max(18 * d * 4, n * d * 10)
+
+
+def head_operands(c: Head):
+    """The tensors of case c (NCHW float64, float32-representable; bf16-representable on the lattice and, for real
+    operands, where the bf16 tape holds them)."""
+    r = rng_for(c.name)
+    o = {"sigmas": torch.tensor(c.sigmas, dtype=F64), "labels": torch.tensor(c.labels(), dtype=torch.int64)}
+    act = (lambda s: normal(r, s)) if c.real else (lambda s: lattice(r, s, -4, 4, 4))
+    wgt = (lambda s: normal(r, s, 0.25)) if c.real else (lambda s: lattice(r, s, -4, 4, 8))
+    if c.op in ("begin", "begin_wgrad"):
+        o["x"] = normal(r, (c.B, 2, c.H, c.W)) if c.real else lattice(r, (c.B, 2, c.H, c.W), 0, 8, 8)
+        if c.op == "begin":
+            o["w"], o["bias"] = wgt((128, 4, 3, 3)), wgt((128,))
+            if not c.real:
+                o["w"][:, 2] = 0.0          # the x coordinate is not on a lattice
+        else:
+            o["dy"] = act((c.B, 128, c.H, c.W))
+            if c.real and c.h16:
+                o["dy"] = bf16_round(o["dy"])
+        return o
+    o["w"] = wgt((2, 128, 3, 3))
+    if c.real:
+        o["x"] = normal(r, (c.B, 128, c.H, c.W))
+        o["scale"] = 0.5 + torch.from_numpy(r.random((c.B, 128)).astype(np.float32)).to(F64)
+        o["shift"] = normal(r, (c.B, 128), 0.5)
+        if c.h16:
+            o["x"] = bf16_round(o["x"])
+    else:
+        o["x"] = lattice(r, (c.B, 128, c.H, c.W), 0, 4, 4)
+        o["scale"] = 2.0 ** lattice(r, (c.B, 128), 0, 1, 1)
+        o["shift"] = lattice(r, (c.B, 128), 0, 2, 4)
+    if c.op == "end":
+        o["bias"] = wgt((2,))
+    else:
+        o["dscore"] = act((c.B, 2, c.H, c.W))
+    return o
+
+
+def begin_prep(x, absval=False, bf16=False):
+    """The begin conv's 4-channel input: R.input_prep (float32 torch.linspace) on the float64 image."""
+    p = R.input_prep(x)          # (a float64 image promotes the float32 coordinates on concatenation)
+    if absval:
+        p = p.abs()
+    return bf16_round(p) if bf16 else p
+
+
+def _pad1(t):
+    return F.pad(t, (1, 1, 1, 1))
+
+
+def head_reference(c: Head, o, mode="fp32", absval=False, mutate=None):
+    """{'out'} (begin, end), {'dw', 'db'} (begin_wgrad) or {'g', 'dw', 'db'} (end_bwd) in float64.  mode 'bf16' on real
+    operands of the forward kernels: conv input and weights rounded to bf16.  absval: the S of the gates.
+    mutate(name, tensor) -> tensor, a deliberately wrong operand (tests/test_kernel_ref_cpu.py), is offered 'prep' (the
+    begin conv's 4-channel input), 'pad' (the zero-padded conv input), 'pad_d' (the zero-padded dscore / sigma of the
+    end data gradient) and 'sigma' (the [B] sigmas of the images)."""
+    A = (lambda t: t.abs()) if absval else (lambda t: t)
+    M = (lambda n, t: mutate(n, t)) if mutate else (lambda n, t: t)
+    bf16 = mode == "bf16" and c.real and c.op in ("begin", "end")
+    rw = lambda t: A(bf16_round(t) if bf16 else t)
+    if c.op == "begin":
+        a = M("pad", _pad1(M("prep", begin_prep(o["x"], absval, bf16))))
+        return {"out": F.conv2d(a, rw(o["w"]), A(o["bias"]))}
+    if c.op == "begin_wgrad":
+        a = M("pad", _pad1(M("prep", begin_prep(o["x"], absval))))
+        dy = A(o["dy"])
+        w = torch.zeros(128, 4, 3, 3, dtype=dy.dtype, requires_grad=True)
+        (dw,) = torch.autograd.grad(F.conv2d(a, w), w, dy)
+        return {"dw": dw, "db": dy.sum(dim=(0, 2, 3))}
+    sig = M("sigma", o["sigmas"][o["labels"]].clone())[:, None, None, None]
+    ec = c.end_case()
+    a = M("pad", _pad1(prologue(ec, o, absval, bf16)))
+    if c.op == "end":
+        return {"out": F.conv2d(a, rw(o["w"]), A(o["bias"])) / sig}
+    dend = A(o["dscore"]) / sig
+    w = torch.zeros(2, 128, 3, 3, dtype=dend.dtype, requires_grad=True)
+    (dw,) = torch.autograd.grad(F.conv2d(a, w), w, dend)
+    # the adjoint of the zero-padded conv, written out (so that the padding can be mutated): a correlation of the
+    # padded gradient with the flipped, transposed weights; test_kernel_ref_cpu.py checks it against autograd
+    da = F.conv2d(M("pad_d", _pad1(dend)), A(o["w"]).flip(2, 3).transpose(0, 1).contiguous())
+    h = o["x"] * o["scale"][:, :, None, None] + o["shift"][:, :, None, None]
+    return {"g": da * elu_grad(h, 1), "dw": dw, "db": dend.sum(dim=(0, 2, 3))}
+
+
+def head_finish(c: Head, ref):
+    """A bf16 output tensor of an exact (lattice) result is that result rounded once."""
+    if c.h16 and not c.real:
+        key = {"begin": "out", "end_bwd": "g"}.get(c.op)
+        if key:
+            ref = dict(ref)
+            ref[key] = bf16_round(ref[key])
+    return ref
+
+
+def head_gate(c: Head, o, mode, ref):
+    """Elementwise bound on |gpu - ref| per output tensor: zero (equality) on lattice operands -- but the coordinate
+    channels of begin_wgrad's dw, which take the fp32 gate -- and the module docstring's table on real ones."""
+    g = {k: torch.zeros_like(v) for k, v in ref.items()}
+    if not c.real and c.op != "begin_wgrad":
+        return g
+    S = head_reference(c, o, absval=True)
+    fwd = c.op in ("begin", "end")
+    for k in ref:
+        rel = c.K(k) * EPS24 + (2.0 ** -15 if (mode == "fp32x3" and fwd) else 0.0)
+        g[k] = rel * S[k]
+    if not c.real:
+        g["dw"][:, :2] = 0.0
+        g["db"] = torch.zeros_like(ref["db"])
+        return g
+    if mode == "bf16" and fwd:
+        if c.op == "begin":
+            flip = 2.0 ** -8 * begin_prep(o["x"]).abs().max() * o["w"].abs().max()
+        else:
+            flip = 2.0 ** -8 * prologue(c.end_case(), o).abs().max() * o["w"].abs().max() / \
+                o["sigmas"][o["labels"]][:, None, None, None]
+        g["out"] = g["out"] + flip
+    key = {"begin": "out", "end_bwd": "g"}.get(c.op)
+    if c.h16 and key:
+        g[key] = g[key] + 2.0 ** -8 * ref[key].abs()
+    return g
+
+
+# ---- single-term mutants of the head kernels (each a mutate(name, tensor) of head_reference)
+def head_mutant_pad_row(c: Head):
+    """The zero padding above image 0 replaced by the clamped border value (what an unselected clamped load gives)."""
+    def mut(name, t):
+        if name in ("pad", "pad_d"):
+            t = t.clone()
+            t[0, :, 0, 1:-1] = t[0, :, 1, 1:-1]
+        return t
+    return mut
+
+
+def head_mutant_pad_col(c: Head):
+    """The zero padding left of image 0 replaced by the clamped border value."""
+    def mut(name, t):
+        if name in ("pad", "pad_d"):
+            t = t.clone()
+            t[0, :, 1:-1, 0] = t[0, :, 1:-1, 1]
+        return t
+    return mut
+
+
+def head_mutant_coord_swap(c: Head):
+    """The two coordinate channels of the begin conv's input swapped."""
+    def mut(name, t):
+        return t[:, [0, 1, 3, 2]].contiguous() if name == "prep" else t
+    return mut
+
+
+def head_mutant_tap(c: Head):
+    """One tap read one pixel off: one channel of pixel (0, 0) of image 0 takes the value of pixel (0, 1) -- the
+    channel where the two differ most; on the lattice channel 0, one unit (1/4) off."""
+    def mut(name, t):
+        if name in ("pad", "pad_d"):
+            t = t.clone()
+            if c.real:
+                ch = int((t[0, :, 1, 2] - t[0, :, 1, 1]).abs().argmax())
+                t[0, ch, 1, 1] = t[0, ch, 1, 2]
+            else:
+                t[0, 0, 1, 1] += 0.25
+        return t
+    return mut
+
+
+def head_mutant_sigma(c: Head):
+    """Image 1 divided by image 0's sigma."""
+    def mut(name, t):
+        if name == "sigma":
+            t = t.clone()
+            t[1] = t[0]
+        return t
+    return mut
+
+
+HEAD_MUTANTS = {"pad_row": head_mutant_pad_row, "pad_col": head_mutant_pad_col, "coord_swap": head_mutant_coord_swap,
+                "tap": head_mutant_tap, "sigma": head_mutant_sigma}
+
+
+# ---- DSM loss (losses/dsm.py:67-119): score, noise, mask [B][n_img]; sigma [B]
+# real sigmas with an exact float32 square, so that 1 / sigma^2 carries ONE rounding (the dscore gate counts it)
+DSM_SIGMAS = (0.75, 13.0, 1.625)
+
+
+def dsm_operands(name, B, n_img, lattice_case=False, zero_image=None):
+    r = rng_for(name)
+    if lattice_case:        # exactly n_img ones over the batch: scale = n_img / count * sigma^p / B = sigma^p / 2 at B = 2
+        assert B == 2
+        mask = np.zeros(B * n_img)
+        mask[r.permutation(B * n_img)[:n_img]] = 1.0
+        return {"score": lattice(r, (B, n_img), -4, 4, 4), "noise": lattice(r, (B, n_img), -4, 4, 4),
+                "mask": torch.from_numpy(mask.reshape(B, n_img)).to(F64), "sigma": torch.tensor((0.5, 2.0), dtype=F64)}
+    sigma = torch.tensor(DSM_SIGMAS[:B], dtype=F64)
+    noise = (normal(r, (B, n_img)) * sigma[:, None]).to(torch.float32).to(F64)
+    mask = torch.from_numpy((r.random((B, n_img)) > 0.3).astype(np.float64))
+    if zero_image is not None:
+        mask[zero_image] = 0.0
+    return {"score": normal(r, (B, n_img)), "noise": noise, "mask": mask, "sigma": sigma}
+
+
+def dsm_reference(o, power, per_image_count=False):
+    """{'loss', 'loss_per', 'dscore'} in float64: R.dsm_loss with its per-image terms kept, and its autograd.
+    per_image_count: the mutant that divides each image by its own mask count instead of the batch's."""
+    s = o["score"].clone().requires_grad_(True)
+    sig, m = o["sigma"][:, None], o["mask"]
+    target = -1 / (sig ** 2) * o["noise"]
+    count = m.sum(dim=-1) * m.shape[0] if per_image_count else m.sum()
+    per = 1 / 2. * (((m * (s - target)) ** 2).sum(dim=-1) * m.shape[-1] / count) * o["sigma"] ** power
+    loss = per.mean(dim=0)
+    (d,) = torch.autograd.grad(loss, s)
+    return {"loss": loss.detach(), "loss_per": per.detach(), "dscore": d}
+
+
+def dsm_gate(o, power):
+    """dscore = scale * mask * mask * (score - target), scale = n_img / count * sigma^p / B taken in double: the
+    reciprocal 1 / sigma^2, the product with the noise, the subtraction and the final rounding -- 4 float32 roundings
+    of (|score| + |target|) * scale.  loss, loss_per: relative 2^-22 (sums of non-negative terms in double; only the
+    per-block partials and the result are rounded to float32)."""
+    sig, m = o["sigma"][:, None], o["mask"]
+    scale = m.shape[-1] / m.sum() * sig ** power / m.shape[0]
+    return 4 * EPS24 * (o["score"].abs() + (o["noise"] / sig ** 2).abs()) * scale * m
+
+
+def dsm_lattice_bound(n_img):
+    """r = score + noise / sigma^2 in units of 1/16, |r| <= 5: r^2 <= 6400 units of 1/256, at most ceil(n_img / 64 / 256)
+    * 256 of them in one block's partial."""
+    return 6400 * 256 * -(-n_img // (64 * 256))

@@ -5,14 +5,23 @@
 * a float32 torch-CPU evaluation of every real-valued case passes the fp32 gate;
 * for each conv direction, a reference with ONE misplaced term -- a border pixel read one lattice unit off, the wrap
   column of one row taken as zero, one channel pair swapped in one tile -- fails the gate of every mode, on the
-  smallest case of each class: the gates see a single-term error.
+  smallest case of each class: the gates see a single-term error;
+* the same for the head and tail kernels (begin / end conv, their backward kernels, the DSM loss): lattice cases exact
+  in float32 and below 2^24 units, real cases within the fp32 gate, the written-out references equal to autograd and to
+  the oracle's own functions, and single-term mutants -- zero padding replaced by the clamped border value in one border
+  row or column, the coordinate channels swapped, one tap one pixel off, image 1 divided by image 0's sigma, the
+  per-image mask count instead of the batch's -- failing the gate of every mode.
 """
+import dataclasses
+
 import pytest
 import torch
 
 import kernel_ref as KR
 import test_gpu_kernels_aux as TA
 import test_gpu_kernels_conv as TC
+import test_gpu_kernels_head as TH
+from kernel_ref import Head
 
 CASES = [c for c, _ in TC.CASES]
 SMALL = [c for c in CASES if c.name.endswith("-a")]
@@ -141,3 +150,151 @@ def test_inpp_scale_shift_restates_instance_norm_pp():
     mean, var = KR.combine_stats(TA._groups(x, 64), 64)
     gm, gv = KR.stats_gate(x)
     assert ((mean - x.mean(dim=(2, 3))).abs() <= gm).all() and ((var - x.var(dim=(2, 3), unbiased=False)).abs() <= gv).all()
+
+
+# ------------------------------------------------------------------------------------------------ head and tail kernels
+R = KR.R
+F64 = torch.float64
+HEAD = TH.BEGIN + [TH.BEGIN_Q] + [c for c, _ in TH.END] + TH.BACKWARD
+_hid = lambda c: c.name + ("-h16" if c.h16 else "")
+
+
+def _h32(o):
+    return {k: (v.to(F32) if v.dtype == F64 else v) for k, v in o.items()}
+
+
+def test_head_tables_hold_the_cases_the_kernels_need():
+    names = {_hid(c) for c in HEAD}
+    assert len(names) == len(HEAD)
+    for op in KR.HEAD_OPS:
+        mine = [c for c in HEAD if c.op == op]
+        assert any(c.real for c in mine) and any(not c.real for c in mine) and any(c.B > 1 for c in mine), op
+    assert {f for _, forms in TH.END for f in forms} == set(TH.FORMS)
+    assert {c.h16 for c in TH.BACKWARD} == {False, True}
+    for c in HEAD:      # different sigmas per image, out of order
+        assert len(set(c.labels())) == c.B and (c.B < 2 or c.labels() != sorted(c.labels()))
+
+
+@pytest.mark.parametrize("c", HEAD, ids=_hid)
+def test_head_float32_cpu_evaluation_passes_the_gate(c):
+    """Lattice: the bound holds and float32 == float64 (begin_wgrad's coordinate channels: the fp32 gate).  Real:
+    |float32 - float64| within the fp32 gate."""
+    if not c.real:
+        assert c.lattice_bound() < 2 ** 24, c.name
+    o = KR.head_operands(c)
+    ref = KR.head_reference(c, o)
+    gate = KR.head_gate(dataclasses.replace(c, h16=False), o, "fp32", ref)
+    got = KR.head_reference(c, _h32(o))
+    for k in ref:
+        g = got[k].to(F64)
+        exact = gate[k] == 0
+        assert c.real or exact.any()
+        assert torch.equal(g[exact], ref[k][exact]), (c.name, k)
+        assert ((g - ref[k]).abs() <= gate[k]).all(), (c.name, k, float((g - ref[k]).abs().max()))
+    if not c.real and c.op == "begin_wgrad":
+        assert (gate["dw"][:, :2] == 0).all() and (gate["db"] == 0).all() and (gate["dw"][:, 2:] > 0).all()
+    if not c.real and c.h16:      # every operand the bf16 tape holds is bf16-representable
+        for k in ("x", "dy"):
+            if k in o:
+                assert torch.equal(KR.bf16_round(o[k]), o[k])
+
+
+def test_head_references_restate_the_oracle_and_autograd():
+    close = lambda a, b: torch.allclose(a, b, rtol=0, atol=1e-11 * float(b.abs().max()))
+    # begin conv and its weight gradient
+    c = Head("restate-begin", "begin", 2, 5, 128, real=True)
+    o = KR.head_operands(c)
+    w, b = o["w"].clone().requires_grad_(True), o["bias"].clone().requires_grad_(True)
+    y = R.conv2d(R.input_prep(o["x"]), w, b, circular=False)
+    assert close(KR.head_reference(c, o)["out"], y.detach())
+    cw = Head("restate-begin", "begin_wgrad", 2, 8, 64, real=True)
+    ow = KR.head_operands(cw)
+    dw, db = torch.autograd.grad(R.conv2d(R.input_prep(ow["x"]), w, b, circular=False), [w, b], ow["dy"])
+    got = KR.head_reference(cw, ow)
+    assert close(got["dw"], dw) and close(got["db"], db)
+    # end conv: conv_forward on the affine + ELU case, / sigma; its backward: autograd of exactly that
+    c = Head("restate-end", "end_bwd", 3, 16, 64, real=True)
+    o = KR.head_operands(c)
+    o["bias"] = torch.tensor([0.25, -0.5], dtype=F64)
+    sig = o["sigmas"][o["labels"]][:, None, None, None]
+    fwd = KR.head_reference(dataclasses.replace(c, op="end"), o)["out"]
+    assert close(fwd, KR.conv_forward(c.end_case(), o)["out"] / sig)
+    h = (o["x"] * o["scale"][:, :, None, None] + o["shift"][:, :, None, None]).requires_grad_(True)
+    w, b = o["w"].clone().requires_grad_(True), o["bias"].clone().requires_grad_(True)
+    out = R.conv2d(R.elu(h), w, b, circular=False) / sig
+    assert close(fwd, out.detach())
+    g, dw, db = torch.autograd.grad(out, [h, w, b], o["dscore"])
+    got = KR.head_reference(c, o)
+    assert close(got["g"], g) and close(got["dw"], dw) and close(got["db"], db)
+    assert (h < 0).any() and (h > 0).any()          # both ELU branches
+    # DSM loss
+    o = KR.dsm_operands("restate-dsm", 3, 1600, zero_image=1)
+    for p in (0, 2):
+        ref = KR.dsm_reference(o, p)
+        want = R.dsm_loss(o["score"], o["sigma"][:, None], o["noise"], o["mask"], p)
+        assert abs(ref["loss"] - want) <= 1e-13 * want and ref["loss_per"][1] == 0 and (ref["dscore"][1] == 0).all()
+
+
+def _mutant_rows():
+    bwd = [("fp32", False), ("fp32", True)]
+    pads = ("pad_row", "pad_col", "tap")
+    rows = []
+    for real in (False, True):
+        t = dict(real=real)
+        rows += [
+            (Head("begin-a", "begin", *TH.BEGIN_SHAPES["a"], **t), TH.FORMS, pads + ("coord_swap",), ("out",)),
+            (Head("end-mfma-a", "end", *TH.END_MFMA["a"], **t), TH.FORMS[1:], pads, ("out",)),
+            (Head("end-direct-a", "end", *TH.END_DIRECT["a"], **t), TH.FORMS[:1], pads, ("out",)),
+            (Head("end-mfma-b", "end", *TH.END_MFMA["b"], **t), TH.FORMS[1:], ("sigma",), ("out",)),
+            (Head("begin_wgrad-a", "begin_wgrad", *TH.BWG["a"], **t), bwd, pads + ("coord_swap",), ("dw",)),
+            (Head("end_bwd-a", "end_bwd", *TH.EBW["a"], **t), bwd, pads, ("g", "dw")),
+            (Head("end_bwd-b", "end_bwd", *TH.EBW["b"], **t), bwd, ("sigma",), ("g", "dw", "db")),
+        ]
+    return [pytest.param(c, forms, m, keys, id=f"{c.name}{'-real' if c.real else ''}-{m}") for c, forms, ms, keys in rows for m in ms]
+
+
+@pytest.mark.parametrize("c,forms,mutant,keys", _mutant_rows())
+def test_a_single_wrong_term_fails_every_gate_of_the_head_kernels(c, forms, mutant, keys):
+    for mode, h16 in forms:
+        cc = dataclasses.replace(c, h16=h16)
+        o = KR.head_operands(cc)
+        ref = KR.head_finish(cc, KR.head_reference(cc, o, mode))
+        gate = KR.head_gate(cc, o, mode, ref)
+        bad = KR.head_finish(cc, KR.head_reference(cc, o, mode, mutate=KR.HEAD_MUTANTS[mutant](cc)))
+        for k in keys:
+            assert ((bad[k] - ref[k]).abs() > gate[k]).any(), f"{c.name} {mode} h16={h16} {k}: the {mutant} mutant passes the gate"
+
+
+def dsm_float32(o, power):
+    """The DSM loss in float32 elementwise arithmetic with the sums in double (the order train_aux.hip documents)."""
+    s, z, m, sg = (o[k].to(F32) for k in ("score", "noise", "mask", "sigma"))
+    B, n = s.shape
+    inv2 = 1.0 / (sg * sg)
+    r = m * (s - (-inv2[:, None] * z))
+    count = m.double().sum()
+    scale = n / count * sg.double() ** power / B
+    per = 0.5 * (r.double() ** 2).sum(dim=-1).to(F32).double() * n / count * sg.double() ** power
+    return {"dscore": (scale[:, None] * (m * r).double()).to(F32).double(), "loss_per": per.to(F32).double(),
+            "loss": per.mean().to(F32).double()}
+
+
+def test_dsm_loss_reference_gates_and_mutant():
+    for B, n_img, power in ((1, 1600, 2), (3, 2 * 7 * 1171, 0), (3, 1600, 2)):
+        o = KR.dsm_operands(f"dsm-cpu-{B}-{n_img}", B, n_img, zero_image=1 if B == 3 else None)
+        ref, gate, got = KR.dsm_reference(o, power), KR.dsm_gate(o, power), dsm_float32(o, power)
+        assert ((got["dscore"] - ref["dscore"]).abs() <= gate).all()
+        assert abs(got["loss"] - ref["loss"]) <= 2.0 ** -22 * ref["loss"]
+        assert ((got["loss_per"] - ref["loss_per"]).abs() <= 2.0 ** -22 * ref["loss_per"]).all()
+    assert all(float(torch.tensor(v, dtype=F32) ** 2) == v * v for v in KR.DSM_SIGMAS)      # exact float32 squares
+    # the lattice case: exact
+    assert KR.dsm_lattice_bound(1600) < 2 ** 24
+    o = KR.dsm_operands("dsm-lattice", 2, 1600, lattice_case=True)
+    ref, got = KR.dsm_reference(o, 2), dsm_float32(o, 2)
+    assert torch.equal(got["dscore"], ref["dscore"]) and torch.equal(got["loss_per"], ref["loss_per"].to(F32).double())
+    assert got["loss"] == ref["loss"].to(F32).double()
+    # the mutant: each image divided by its own mask count instead of the batch's
+    o = KR.dsm_operands("dsm-mutant", 3, 1600)
+    ref, gate, bad = KR.dsm_reference(o, 2), KR.dsm_gate(o, 2), KR.dsm_reference(o, 2, per_image_count=True)
+    assert ((bad["dscore"] - ref["dscore"]).abs() > gate).any()
+    assert abs(bad["loss"] - ref["loss"]) > 2.0 ** -22 * ref["loss"]
+    assert ((bad["loss_per"] - ref["loss_per"]).abs() > 2.0 ** -22 * ref["loss_per"]).any()
