@@ -17,64 +17,10 @@ import torch
 import torch.multiprocessing as mp
 
 from oracle import golden_inputs as GI
-from oracle import philox_ref
-from oracle import sampling_ref as S
+from sampler_lockstep import OracleOps, fake_score   # the CPU stand-ins, shared with the lockstep grader
 
 B_ALL, H, W = 8, 64, 128
 SIGMAS = np.array([0.9, 0.6, 0.3], np.float32)
-
-
-class OracleMerger:
-    def __init__(self, n_all, aB, H, W, dev, exist, sky, refmask, toWorld=None, fromWorld=None, origins=None,
-                 o_begin=0, n_out=None):
-        self.aB, self.o_begin, self.n_out = aB, o_begin, n_out
-        self.exist = np.asarray(exist)
-        self.sky = np.asarray(sky).reshape(n_all, 1, H, W)
-        self.refmask = np.asarray(refmask)
-        # origin-offset variant: the origins are already 10*sign(m), which the oracle maps to themselves
-        self.mods = None if origins is None else np.asarray(origins)
-        if origins is None:
-            self.toWorld = np.asarray(toWorld).reshape(n_all, 4, 4)
-            self.fromWorld = np.asarray(fromWorld).reshape(n_all, 4, 4)
-
-    def __call__(self, x_all, sigma, setting, allowance, cc, absmax, new):
-        amax = absmax.view(torch.float32).item()
-        if self.mods is not None:
-            n, xc = S.allforone_merge(x_all.numpy(), self.refmask, self.sky, self.exist, self.mods, self.aB, sigma,
-                                      setting, cc, absmax=amax)
-        else:
-            n, xc = S.kitti_merge(x_all.numpy(), self.refmask, self.sky, self.exist, self.toWorld, self.fromWorld,
-                                  self.aB, sigma, setting, allowance, cc, absmax=amax)
-        sl = slice(self.o_begin, self.o_begin + self.n_out)
-        x_all[sl] = torch.from_numpy(xc[sl])
-        if new is not None:
-            new.copy_(torch.from_numpy(n[sl]))
-
-
-class OracleOps:
-    def langevin(self, x, grad, ref, mask, noise, seed, offset, step, nscale, grad_ref, nan_to_num, lik, absmax):
-        g = S.nan_to_num(grad.numpy()) if nan_to_num else grad.numpy()
-        if noise is None:   # the kernel's Philox stream (seed, counter = offset + element/4)
-            noise = torch.from_numpy(philox_ref.normal(seed, offset, x.numel()).reshape(x.shape))
-        lk = (-mask.numpy()).astype(np.float32) * (x.numpy() - ref.numpy())
-        v = (((x.numpy() + np.float32(step) * g) + np.float32(grad_ref) * lk) + noise.numpy() * np.float32(nscale))
-        x.copy_(torch.from_numpy(v.astype(np.float32)))
-        lik.copy_(torch.from_numpy(lk))
-        absmax.copy_(torch.tensor([np.abs(v[:, 0]).max()], dtype=torch.float32).view(torch.int32))
-
-    def axpy(self, x, g, a, lik, mask, ref, b):
-        if g is not None:
-            x.copy_(((x + np.float32(a) * g) + np.float32(b) * lik))
-        else:
-            x.copy_(x + np.float32(b) * ((-mask).float() * (x - ref)))
-
-    def make_merger(self, *a, **kw):
-        return OracleMerger(*a, **kw)
-
-
-def fake_score(x, y):
-    """Deterministic stand-in for the score net (depends on x and on the label)."""
-    return -(x - 0.5) * (1.0 + 0.01 * y.view(-1, 1, 1, 1).float()) + 0.05 * torch.sin(7 * x)
 
 
 def _inputs():

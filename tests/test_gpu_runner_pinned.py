@@ -43,6 +43,8 @@ def _layout(x):
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["HDVMine_Line.yml", "HDVMine_Circle.yml"])
 def test_runner_files_equal_oracle_samplers(tmp_path, name, monkeypatch):
+    """The runner's files against the oracle samplers (module docstring).  A trajectory check, hence the mismatch
+    fraction; the per-step exact gate (no fraction) lives in tests/test_gpu_sampler_lockstep.py."""
     from oracle import philox_ref
     from oracle import sampling_ref as S
     from oracle import scorenet_ref as R
