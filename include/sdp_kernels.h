@@ -141,6 +141,12 @@ int sdpk_end_conv_backward(const float* dscore, const float* sigmas, const int64
                            void* stream);
 size_t sdpk_head_wgrad_part_floats(int B, int H, int W);
 
+/* ---- the data front end (projection.hip) */
+/* the row-sequential sky / obfuscation scan of sdp_range_project (datasets/lidar_utils.py:283-306), one launch:
+ * xy: float64 [H][W], the flipped planar-range image (2057.701 where empty); obf, sky: u8 [H][W], sky all 0 as the
+ * reference clears it.  3 <= H, 1 <= W <= 1024 */
+int sdpk_range_sky_scan(const double* xy, int H, int W, uint8_t* obf, uint8_t* sky, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -199,4 +199,8 @@ int sdpk_end_conv_backward(const float* dscore, const float* sigmas, const int64
 
 size_t sdpk_head_wgrad_part_floats(int B, int H, int W) { return head_wgrad_part_floats(B, H, W); }
 
+int sdpk_range_sky_scan(const double* xy, int H, int W, uint8_t* obf, uint8_t* sky, void* stream) {
+  return done(range_sky_scan(xy, H, W, obf, sky, S(stream)), "sdpk_range_sky_scan");
+}
+
 }  // extern "C"

@@ -87,5 +87,8 @@ size_t wgrad_part_floats(int S, int Cin, int Cout, int ks);
 // h16: a.in and a.dy hold bf16 elements (the training tape; bf16 mode)
 hipError_t conv_wgrad(int mode, WgradArgs a, int ks, float* out, float* bias_out, int accumulate, hipStream_t st,
                       const char** why, bool h16 = false);
+// the sky / obfuscation scan of the range projection (projection.hip) over its flipped xy image [H][W] float64:
+// obf, sky [H][W] u8; 3 <= H, 1 <= W <= 1024 (else hipErrorInvalidValue)
+hipError_t range_sky_scan(const double* xy, int H, int W, uint8_t* obf, uint8_t* sky, hipStream_t st);
 
 }  // namespace sdp

@@ -160,12 +160,22 @@ __global__ __launch_bounds__(256) void proj_init_kernel(unsigned long long* __re
   }
 }
 
-size_t range_project_ws_bytes(int H, int W) { return (size_t)H * W * (8 + 4 + 8); }
+hipError_t range_sky_scan(const double* xy, int H, int W, uint8_t* obf, uint8_t* sky, hipStream_t st) {
+  if (!xy || !obf || !sky || H < 3 || W < 1 || W > 1024) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(proj_sky_kernel, dim3(1), dim3(((W + 63) / 64) * 64), 0, st, xy, H, W, obf, sky);
+  return hipGetLastError();
+}
+
+// dbest (8 n), ibest (4 n, padded to the 8-byte alignment of what follows), xy (8 n): the layout of range_project
+size_t range_project_ws_bytes(int H, int W) {
+  const size_t n = (size_t)H * W;
+  return n * 8 + ((n * 4 + 7) / 8) * 8 + n * 8;
+}
 
 hipError_t range_project(const double* pts, int N, int stride, int has_int, double ox, double oy, double oz, int H,
                          int W, double* depth, double* inten, uint8_t* obf, uint8_t* sky, int64_t* index, void* ws,
                          hipStream_t st) {
-  if (W > 1024 || H < 3 || stride < 3 || (has_int && stride < 4)) return hipErrorInvalidValue;
+  if (W < 1 || W > 1024 || H < 3 || stride < 3 || (has_int && stride < 4)) return hipErrorInvalidValue;
   ProjGeom g;
   g.H = H;
   g.W = W;
@@ -191,7 +201,7 @@ hipError_t range_project(const double* pts, int N, int stride, int has_int, doub
   hipLaunchKernelGGL(proj_pixel_kernel, dim3((int)((n + 255) / 256)), dim3(256), 0, st, pts, stride, has_int, g, ibest,
                      depth, inten, xy, index);
   if (obf)   // callers that only need the depth / intensity (a goal scan) skip the sequential scan
-    hipLaunchKernelGGL(proj_sky_kernel, dim3(1), dim3(((W + 63) / 64) * 64), 0, st, xy, H, W, obf, sky);
+    return range_sky_scan(xy, H, W, obf, sky, st);
   return hipGetLastError();
 }
 

@@ -55,6 +55,7 @@ SIGS = {
     "sdpk_begin_conv_wgrad": (I, [P, P, P, P, P, I, I, I, I, P]),
     "sdpk_end_conv_backward": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, P]),
     "sdpk_head_wgrad_part_floats": (SZ, [I, I, I]),
+    "sdpk_range_sky_scan": (I, [P, I, I, P, P, P]),
 }
 
 _bound = None

@@ -778,3 +778,134 @@ def dsm_lattice_bound(n_img):
     """r = score + noise / sigma^2 in units of 1/16, |r| <= 5: r^2 <= 6400 units of 1/256, at most ceil(n_img / 64 / 256)
     * 256 of them in one block's partial."""
     return 6400 * 256 * -(-n_img // (64 * 256))
+
+
+# ---- the data front end (projection.hip, kitti_view.hip): float64 numpy --------------------------------------------
+
+VIEW_MAX_RANGE = 2057.701
+BIN_EDGE_EPS = 1e-9
+
+
+def bin_edge_guard(points, origin, H, W, eps=BIN_EDGE_EPS):
+    """The precondition of every exact comparison with sdp_range_project, from the reference's arithmetic alone: no
+    finite point's fractional column or row, moved by +-eps bins, changes its decision (the clamped pixel together
+    with in-grid or excluded).  The device's atan2 may differ from libm by a few ulp of at most pi, ~1e-15 rad, i.e.
+    ~3e-13 bins at the finest step used (W = 1024); the subtraction and the division add about as much again; 1e-9
+    leaves three orders of margin.  A point AT the origin (x = y = 0 after the subtraction) is checked for its row only:
+    its azimuth atan2(+-0, +-0) is not computed but fixed by IEEE 754 / C Annex F at exactly 0 or +-pi, and the column
+    W/2 - 1/2 it gives (a bin edge, always) is then the same correctly rounded subtraction and division, rounded half
+    to even, on every conforming implementation.
+    Returns the smallest distance to a deciding bin edge (inf: no such edge)."""
+    from oracle import projection_ref as PR
+    p = np.asarray(points, np.float64)[:, :3] - np.asarray(origin, np.float64)
+    p = p[np.isfinite(p).all(axis=1)]
+    hA, vA, hMin, vMin = PR.geometry(H, W)
+    at_origin = (p[:, 0] == 0) & (p[:, 1] == 0)
+    cf = ((np.arctan2(p[:, 1], p[:, 0]) - hMin) / hA)[~at_origin]
+    rf = (np.arctan2(p[:, 2], np.sqrt(np.square(p[:, 0]) + np.square(p[:, 1]))) - vMin) / vA
+
+    def decide(f, n):
+        b = np.clip(np.round(f), 0, n - 1)
+        return b, b > 0
+
+    margin = np.inf
+    for f, n, what in ((cf, W, "column"), (rf, H, "row")):
+        b0, in0 = decide(f, n)
+        for s in (-eps, eps):
+            b, ing = decide(f + s, n)
+            bad = (b != b0) | (ing != in0)
+            assert not bad.any(), f"{int(bad.sum())} points within {eps} bins of a {what} edge at {H}x{W}: reseed"
+        # distance to the nearest half-integer that separates two different clamped bins
+        edge = np.floor(f) + 0.5
+        deciding = (edge > 0) & (edge < n - 1)
+        if deciding.any():
+            margin = min(margin, float(np.abs(f - edge)[deciding].min()))
+    return margin
+
+
+def view_finalize_ref(depth, inten, obf, sky, goal_depth, goal_inten, channels, roll, variant, first_view):
+    """The post-processing the datasets' __getitem__ apply to the projection's outputs, statement by statement from
+    kitti360_im_8Batch.py:221-304 (variant 0), kitti360_im_AllForOne.py:253-353 (1),
+    kitti360_im_simultenous_densification.py:230-339 (2, first_view = numberInBatch == 0) and
+    kitti360_im_SceneCompletion.py:388-513 (3; goal_depth may be None).  channels == 2 is return_remission;
+    roll >= 0 is random_roll with that draw, roll < 0 is random_roll off.  All inputs [H][W].
+    Returns (real [C][H][W] float64, notmask [C][H][W] bool, notsky [H][W] bool, goal [C][H][W] float64 or None)."""
+    maxRange = VIEW_MAX_RANGE
+    real = np.array(depth, np.float64)
+    mask = np.array(obf).astype(bool)
+    sky = np.array(sky).astype(bool)
+    colMax = real.shape[1]
+    has_goal = goal_depth is not None
+    mask = np.where(real >= maxRange, 1, mask)
+    real = np.where(real >= maxRange, 0, real) + 0.0001
+    real = np.log2(real + 1) / 6
+    real = np.clip(real, 0, 1)
+    if has_goal:
+        goalDepth = np.where(goal_depth >= maxRange, 0, goal_depth) + 0.0001
+        goalDepth = np.clip(np.log2(goalDepth + 1) / 6, 0, 1)
+        goalDepth = np.expand_dims(goalDepth, axis=0)
+    if roll >= 0:
+        real = np.roll(real, roll, axis=1)
+        mask = np.roll(mask, roll, axis=1)
+        sky = np.roll(sky, roll, axis=1)
+    if channels == 2:
+        # 8Batch:272 and SceneCompletion:472 run this after the sky shift, AllForOne:276-279 and densification:257-258
+        # right here; nothing in between touches the mask except the first-view override below, which comes later in
+        # the only variant that has it
+        mask = np.where(inten >= 1, 1, mask)      # the intensity is NOT rolled yet
+    real = np.expand_dims(real, axis=0)
+    mask = np.expand_dims(mask, axis=0)
+    if variant == 2 and first_view:
+        maskThree = np.zeros_like(real).astype(int)
+        maskThree[:, :, :(colMax // 4)] = 1
+        mask = np.zeros_like(mask)
+        mask = np.logical_or(mask, maskThree)
+    sky[1:] = sky[:-1]
+    sky[1:] = sky[:-1]
+    sky[1:] = sky[:-1]
+    if channels == 2:
+        intensity = np.where(inten >= 1, 0, inten) + 0.0001
+        intensity = np.clip(intensity, 0, 1.0)
+        if roll >= 0:
+            intensity = np.roll(intensity, roll, axis=1)
+        intensity = np.expand_dims(intensity, axis=0)
+        if variant == 3:
+            real = np.concatenate((real, real), axis=0)
+            mask = np.concatenate((mask, np.ones_like(mask)), axis=0)
+        else:
+            real = np.concatenate((real, intensity), axis=0)
+            mask = np.concatenate((mask, mask), axis=0)
+        if has_goal:
+            goalIntensity = np.where(goal_inten >= 1, 0, goal_inten) + 0.0001
+            goalIntensity = np.clip(goalIntensity, 0, 1.0)
+            goalDepth = np.concatenate((goalDepth, np.expand_dims(goalIntensity, axis=0)), axis=0)
+    return real, np.logical_not(mask), np.logical_not(sky), (goalDepth if has_goal else None)
+
+
+def view_finalize_inputs(name, H, W):
+    """Projection-like inputs that reach every branch of the post-processing: ~10 % set sky bits with rows 0-2 and the
+    last three rows among them, a random obf, a third of the depths exactly 2057.701 and some above it, intensities
+    with exactly 1.0, 1.5, 0 and 1 - 2^-24 among uniform(0, 1.2) draws."""
+    r = rng_for("view_finalize-" + name)
+    depth = r.uniform(0.0, 80.0, (H, W))                    # log2(d + 1) / 6 clips to 1 past d = 63
+    depth[r.random((H, W)) < 1 / 3] = VIEW_MAX_RANGE
+    depth[r.random((H, W)) < 0.04] = VIEW_MAX_RANGE + 1.0
+    depth[r.random((H, W)) < 0.02] = 5000.0
+    depth[r.random((H, W)) < 0.02] = 0.0
+    inten = r.uniform(0.0, 1.2, (H, W))
+    for v in (1.0, 1.5, 0.0, 1.0 - 2.0 ** -24):
+        inten[r.random((H, W)) < 0.06] = v
+    pos = r.permutation(H * W)[:7]                          # each special value at least once, whatever the size
+    for k, v in enumerate((1.0, 1.5, 0.0, 1.0 - 2.0 ** -24)):
+        inten.flat[pos[k]] = v
+    for k, v in enumerate((VIEW_MAX_RANGE, VIEW_MAX_RANGE + 1.0, 70.0)):
+        depth.flat[pos[4 + k]] = v
+    obf = (r.random((H, W)) < 0.3).astype(np.uint8)
+    sky = (r.random((H, W)) < 0.1).astype(np.uint8)
+    for row in (0, 1, 2, H - 3, H - 2, H - 1):
+        sky[row, r.integers(0, W)] = 1
+    gd = r.uniform(0.0, 80.0, (H, W))
+    gd[r.random((H, W)) < 0.3] = VIEW_MAX_RANGE
+    gi = r.uniform(0.0, 1.2, (H, W))
+    gi[r.random((H, W)) < 0.1] = 1.0
+    return dict(depth=depth, inten=inten, obf=obf, sky=sky, goal_depth=gd, goal_inten=gi)

@@ -2,15 +2,18 @@
 sdp_range_project / sdp_view_gather / sdp_view_finalize) against the numpy restatement of the
 datasets' __getitem__ (oracle/kitti_ref.py, projection pinned to the reference's outputs).
 
-Bar: masks, sky, index and the pose matrices bit-exact; the float64 images to 1e-13 relative
-(device log2 vs the host libm; the point transform sums the 4 products left to right where
-numpy's matmul goes through BLAS, so coordinates may differ in the last bit -- a pixel
-assignment could only change for a point within one ulp of a bin edge, which these seeded
-scenes do not have)."""
+Bar: masks, sky, index and the pose matrices bit-exact on every pixel; the float64 images to 1e-13
+relative (device log2 vs the host libm).  The point transform sums the 4 products left to right
+where numpy's matmul goes through BLAS, so coordinates may differ in the last bit, and the device
+atan2 from libm's by a few ulp: together below 1e-12 bins.  A pixel assignment could only change
+for a point that close to a bin edge, and every cloud the oracle projects here first passes
+kernel_ref.bin_edge_guard (no point within 1e-9 bins of an edge that decides its pixel), computed
+from the reference's arithmetic alone."""
 import numpy as np
 import pytest
 import torch
 
+import kernel_ref as KR
 from kitti_tree import config, write_tree
 from oracle import kitti_ref
 from sdp import kitti360
@@ -24,6 +27,17 @@ def tree(tmp_path_factory):
     root = str(tmp_path_factory.mktemp("kitti360"))
     write_tree(root, n_poses=24, n_points=40000)
     return root
+
+
+@pytest.fixture(autouse=True)
+def guarded_oracle(monkeypatch):
+    """Every cloud the oracle projects (the view, the goal scan, the densification input) passes the bin-edge guard."""
+    project = kitti_ref.point_cloud_to_range_image
+
+    def guarded(pc, origin, return_remission=False, rowMax=64, colMax=1024):
+        assert KR.bin_edge_guard(pc, origin, rowMax, colMax) > KR.BIN_EDGE_EPS
+        return project(pc, origin, return_remission, rowMax=rowMax, colMax=colMax)
+    monkeypatch.setattr(kitti_ref, "point_cloud_to_range_image", guarded)
 
 
 def _check(got, want):

@@ -10,16 +10,23 @@
   in float32 and below 2^24 units, real cases within the fp32 gate, the written-out references equal to autograd and to
   the oracle's own functions, and single-term mutants -- zero padding replaced by the clamped border value in one border
   row or column, the coordinate channels swapped, one tap one pixel off, image 1 divided by image 0's sigma, the
-  per-image mask count instead of the batch's -- failing the gate of every mode.
+  per-image mask count instead of the batch's -- failing the gate of every mode;
+* the data front end (tests/test_gpu_kernels_frontend.py): ``view_finalize_ref`` bit-equal to the oracle's own dataset
+  tails, the bin-edge guard, the projection's workspace size against its layout, and the GPU module's inputs telling
+  single-term mutants of the references apart (a non-strict compare, a stale column sum, a dropped chain term or a
+  misread batch row in the sky scan; the higher index of a tie, a single grid-stride pass; a rolled intensity test, a
+  2- or 4-row sky shift, an unrolled sky).
 """
 import dataclasses
 
+import numpy as np
 import pytest
 import torch
 
 import kernel_ref as KR
 import test_gpu_kernels_aux as TA
 import test_gpu_kernels_conv as TC
+import test_gpu_kernels_frontend as TF
 import test_gpu_kernels_head as TH
 from kernel_ref import Head
 
@@ -298,3 +305,185 @@ def test_dsm_loss_reference_gates_and_mutant():
     assert ((bad["dscore"] - ref["dscore"]).abs() > gate).any()
     assert abs(bad["loss"] - ref["loss"]) > 2.0 ** -22 * ref["loss"]
     assert ((bad["loss_per"] - ref["loss_per"]).abs() > 2.0 ** -22 * ref["loss_per"]).any()
+
+
+# ---- the view post-processing reference (KR.view_finalize_ref) against the oracle's own dataset tails -------------
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float64).view(np.uint64)
+
+
+def test_view_finalize_inputs_reach_every_branch():
+    for H, W in ((5, 7), (8, 100), (64, 256)):
+        a = KR.view_finalize_inputs(f"{H}x{W}", H, W)
+        assert a["sky"][:3].any() and a["sky"][-3:].any() and 0.05 < a["sky"].mean() < 0.25    # 5x7: 6 forced bits
+        assert (a["depth"] == KR.VIEW_MAX_RANGE).any() and (a["depth"] > KR.VIEW_MAX_RANGE).any()
+        assert ((a["depth"] > 63) & (a["depth"] < KR.VIEW_MAX_RANGE)).any()        # the upper clip of the depth code
+        for v in (1.0, 1.5, 0.0, 1.0 - 2.0 ** -24):
+            assert (a["inten"] == v).any(), v
+        # the "unrolled intensity against rolled mask" rule decides pixels under a roll by one column
+        hit = (a["inten"] >= 1) & ~((np.roll(a["inten"], 1, axis=1) >= 1))
+        assert hit.any()
+
+
+@pytest.mark.parametrize("variant", [0, 1, 2])
+@pytest.mark.parametrize("roll", [None, 0, 1, 99])
+@pytest.mark.parametrize("first_view", [0, 1])
+def test_view_finalize_ref_equals_the_kitti_oracle_tail(variant, roll, first_view):
+    from oracle import kitti_ref
+    H, W = 8, 100
+    a = KR.view_finalize_inputs("pin", H, W)
+    want = kitti_ref._post(a["depth"], a["inten"], a["obf"].astype(bool), a["sky"].astype(bool), a["goal_depth"],
+                           a["goal_inten"], H, W, roll, variant, 0 if first_view else 1)
+    got = KR.view_finalize_ref(a["depth"], a["inten"], a["obf"], a["sky"], a["goal_depth"], a["goal_inten"], 2,
+                               -1 if roll is None else roll, variant, first_view)
+    real, notmask, notsky, goal = got
+    assert real.shape == want[0].shape == (2, H, W) and np.array_equal(_bits(real), _bits(want[0]))
+    assert notmask.shape == (2, H, W) and np.array_equal(notmask, want[1])
+    assert np.array_equal(notsky[None], want[2])
+    assert np.array_equal(_bits(goal), _bits(want[3]))
+    assert not notsky.all() and not notmask.all() and notmask.any()
+
+
+@pytest.mark.parametrize("roll", [None, 0, 1, 99])
+def test_view_finalize_ref_equals_the_completion_oracle_tail(roll, tmp_path, monkeypatch):
+    """oracle/completion_ref.item with its loading, subsampling, origin and projection replaced by the seeded arrays:
+    what remains is its post-processing tail, unchanged."""
+    from oracle import completion_ref as CR
+    H, W = 8, 100
+    a = KR.view_finalize_inputs("pin3", H, W)
+    np.save(tmp_path / "scan.npy", np.zeros((4, 3)))
+    np.save(tmp_path / "final.npy", np.zeros((2, 4)))
+    monkeypatch.setattr(CR, "grid_sub_sampling_ref", lambda p, dl=0.05: p)
+    monkeypatch.setattr(CR, "view_origin", lambda scan, nib, mods: np.zeros(3))
+    monkeypatch.setattr(CR, "point_cloud_to_range_image", lambda *_: (
+        a["depth"].copy(), a["inten"].copy(), a["obf"].astype(bool), 0, a["sky"].astype(bool), np.zeros((H, W))))
+    want = CR.item(str(tmp_path / "scan.npy"), str(tmp_path / "final.npy"), 0, np.zeros((1, 3)), H, W, roll)
+    real, notmask, notsky, goal = KR.view_finalize_ref(a["depth"], a["inten"], a["obf"], a["sky"], None, None, 2,
+                                                       -1 if roll is None else roll, 3, 0)
+    assert goal is None
+    assert real.shape == want[0].shape and np.array_equal(_bits(real), _bits(want[0]))
+    assert np.array_equal(_bits(real[0]), _bits(real[1]))
+    assert notmask.shape == want[1].shape and np.array_equal(notmask, want[1]) and not notmask[1].any()
+    assert np.array_equal(notsky[None], want[2])
+
+
+def test_view_finalize_ref_one_channel_is_the_depth_path_alone():
+    """channels == 1 is return_remission off: no intensity test, one channel (8Batch:268-291 skipped)."""
+    H, W = 8, 100
+    a = KR.view_finalize_inputs("pin1", H, W)
+    for variant in range(4):
+        r1 = KR.view_finalize_ref(a["depth"], None, a["obf"], a["sky"], a["goal_depth"], None, 1, 3, variant, 0)
+        r2 = KR.view_finalize_ref(a["depth"], np.zeros((H, W)), a["obf"], a["sky"], a["goal_depth"], np.zeros((H, W)),
+                                  2, 3, variant, 0)
+        assert r1[0].shape == r1[1].shape == r1[3].shape == (1, H, W)
+        assert np.array_equal(_bits(r1[0][0]), _bits(r2[0][0])) and np.array_equal(r1[1][0], r2[1][0])
+        assert np.array_equal(r1[2], r2[2]) and np.array_equal(_bits(r1[3][0]), _bits(r2[3][0]))
+
+
+def test_bin_edge_guard_passes_the_goldens_and_sees_an_edge_point():
+    from oracle import golden_inputs as GI
+    from oracle import projection_ref as PR
+    for tag, (n, origin) in GI.PROJECTION_CASES.items():
+        assert KR.bin_edge_guard(GI.projection_cloud(tag, n), origin, 64, 1024) > KR.BIN_EDGE_EPS
+    hA, vA, hMin, vMin = PR.geometry(20, 100)
+    for dc, dr in ((0.5 + 1e-11, 0.0), (0.0, 0.5 - 1e-11)):          # 1e-11 bins off a column / a row edge
+        h, v = hMin + (40 + dc) * hA, vMin + (7 + dr) * vA
+        p = np.array([[10 * np.cos(h), 10 * np.sin(h), 10 * np.tan(v)]])
+        with pytest.raises(AssertionError):
+            KR.bin_edge_guard(p, np.zeros(3), 20, 100)
+    # the clamp absorbs the last half bin: a point on the seam (column W - 1/2) decides nothing
+    assert KR.bin_edge_guard(np.array([[-5.0, 0.0, 0.0], [-5.0, -0.0, 0.0]]), np.zeros(3), 20, 100) > 0.1
+
+
+def test_projection_workspace_holds_its_layout_at_odd_pixel_counts():
+    """sdp_range_project lays out 8 n bytes of depth bits, 4 n of winner indices padded to 8-byte alignment, and 8 n of
+    planar ranges: at an odd n = H * W the padding is 4 bytes that n * 20 does not have."""
+    import ctypes as C
+
+    from sdp import _lib
+    for H, W in ((5, 7), (3, 1), (64, 1023), (64, 1024), (20, 100)):
+        n, got = H * W, _lib.SZ()
+        _lib.check(_lib.lib().sdp_range_project_workspace_size(H, W, C.byref(got)), "ws")
+        assert got.value >= 8 * n + 8 * ((4 * n + 7) // 8) + 8 * n, (H, W, got.value)
+
+
+# ---- the front-end inputs tell single-term mutants of the references apart (tests/test_gpu_kernels_frontend.py) ----
+
+def _sky_scan_mutant(xy, kind):
+    """oracle.projection_ref.sky_scan with ONE change: 'ge' compares x >= md + 5; 'stale' takes the left neighbour's
+    count from the previous row (a 3-column sum read before the row buffer is rewritten); 'nochain' drops the
+    `and sky[row - 1]` of the still-sky chain; 'batch' reads row 2 + 16 + 1, the first of the second 16-row batch, as 0."""
+    H, W = xy.shape
+    md = np.zeros(W) + TF.MAXR
+    prev, e_prev = np.ones(W, bool), np.zeros(W + 2, int)
+    obf = np.zeros((H, W), bool)
+    over = (lambda x, m: x >= m + 5) if kind == "ge" else (lambda x, m: x > m + 5)
+    for row in range(2, H - 1):
+        obf[row] = over(xy[row], md)
+        nxt = np.zeros(W) if kind == "batch" and row + 1 == 19 else xy[row + 1]
+        e = np.concatenate(([0], (xy[row] != md).astype(int) + (xy[row - 1] != md) + (nxt != md), [0]))
+        left = e_prev[:-2] if kind == "stale" else e[:-2]
+        cur = (e[1:-1] + left + e[2:] <= 1) & (True if kind == "nochain" else prev)
+        md = np.where(cur, md, np.minimum(xy[row], md))
+        prev, e_prev = cur, e
+    obf[-1] = over(xy[-1], md)
+    return obf
+
+
+@pytest.mark.parametrize("H,W", [s for s in TF.SKY_SHAPES if s[0] >= 20])
+def test_the_sky_scan_images_tell_single_term_mutants_apart(H, W):
+    xy = TF.sky_image(H, W)
+    want = TF.PR.sky_scan(xy)[0]
+    assert np.array_equal(_sky_scan_mutant(xy, None), want)
+    for kind in ("ge", "stale", "nochain") + (("batch",) if H > 20 else ()):      # H = 20: row 19 is the last row
+        assert (_sky_scan_mutant(xy, kind) != want).any(), kind
+
+
+def test_the_lattice_clouds_tell_the_tie_rule_and_the_z_buffer_apart():
+    for H, W in ((20, 100), (16, 128)):
+        pts = TF.lattice_cloud(H, W)
+        ref = TF.reference(pts, np.zeros(3), H, W)
+        # the highest index of a tie instead of the lowest: the oracle on the reversed cloud, indices mapped back
+        rev = TF.reference(pts[::-1], np.zeros(3), H, W)["index"]
+        rev = np.where(rev >= 0, len(pts) - 1 - rev, rev)
+        assert int((rev != ref["index"]).sum()) == TF.tie_pixels(pts, ref) >= 10
+        # the farther point of a pixel instead of the nearer: depth negated in the sort is not expressible through the
+        # oracle, but dropping the winners must bring the losers up -- the cloud has pixels with more than one point
+        win = ref["index"][ref["index"] >= 0]
+        rest = TF.reference(np.delete(pts, win, axis=0), np.zeros(3), H, W)
+        assert (rest["index"] >= 0).sum() >= 100
+
+
+def test_the_two_pass_cloud_needs_its_second_pass():
+    pts, H, W, cross = TF.two_pass_cloud()
+    assert len(pts) > TF.GRID_CAP and cross.sum() == 600
+    ref = TF.reference(pts, np.zeros(3), H, W)
+    first_only = TF.reference(pts[:TF.GRID_CAP], np.zeros(3), H, W)     # a loop that stops after one pass
+    assert (first_only["index"] != ref["index"]).sum() >= 150
+    rev = TF.reference(pts[::-1], np.zeros(3), H, W)["index"]            # the higher index of each tie
+    rev = np.where(rev >= 0, len(pts) - 1 - rev, rev)
+    assert (rev != ref["index"]).sum() == 600 and (rev[rev != ref["index"]] >= TF.GRID_CAP).sum() >= 300
+
+
+def test_the_finalize_inputs_tell_single_term_mutants_apart():
+    for H, W in ((5, 7), (8, 100), (64, 256)):
+        a = KR.view_finalize_inputs(f"{H}x{W}", H, W)
+        args = (a["obf"], a["sky"], a["goal_depth"], a["goal_inten"], 2)
+        real, notmask, notsky, _ = KR.view_finalize_ref(a["depth"], a["inten"], *args, 1, 0, 0)
+        # the intensity test on the ROLLED intensity
+        assert (KR.view_finalize_ref(a["depth"], np.roll(a["inten"], 1, axis=1), *args, 1, 0, 0)[1] != notmask).any()
+        # no intensity test at all (channels 1), and the intensity cut left out of channel 2
+        one = KR.view_finalize_ref(a["depth"], None, a["obf"], a["sky"], a["goal_depth"], None, 1, 1, 0, 0)
+        assert (one[1][0] != notmask[0]).any()
+        assert (real[1] == 0.0001).sum() >= 3 and (np.roll(a["inten"], 1, axis=1) >= 1)[real[1] == 0.0001].any()
+        # the sky: unrolled, or shifted by 2 or by 4 rows instead of 3
+        sky = np.roll(a["sky"].astype(bool), 1, axis=1)
+        shift = lambda s, k: np.concatenate([np.repeat(s[:1], k, axis=0), s[:-k]])
+        assert np.array_equal(notsky, ~shift(sky, 3))
+        for bad in (~shift(a["sky"].astype(bool), 3), ~shift(sky, 2), ~shift(sky, 4)):
+            assert (bad != notsky).any()
+        # the first-view mask of the densification variant, and the all-masked second channel of the completion one
+        dens = KR.view_finalize_ref(a["depth"], a["inten"], *args, 1, 2, 1)[1]
+        assert (dens != notmask).any() and dens[0, :, :W // 4].sum() == 0 and dens[0, :, W // 4:].all()
+        assert not KR.view_finalize_ref(a["depth"], a["inten"], a["obf"], a["sky"], None, None, 2, 1, 3, 0)[1][1].any()
