@@ -23,6 +23,8 @@
  *   sdp_adam_ema_step      optimizer.step() (Adam, losses/__init__.py:10-20) + EMAHelper.update (models/ema.py:16-21)
  *   sdp_optim_ema_step     optimizer.step() of Adam / RMSprop / SGD (get_optimizer, losses/__init__.py:3-13) + EMA
  *   sdp_range_project      point_cloud_to_range_image                       datasets/lidar_utils.py:54-347
+ *   sdp_range_unproject    range image -> fused point cloud                 MeasureResults/SceneCompleter.py:43-70,
+ *                                                                             105-121, 259-264
  *   sdp_view_transform     pose chain fromWorld @ (toWorld @ p)             datasets/kitti360_im_8Batch.py:146-190
  *   sdp_view_gather        scanPoints[index[index >= 0]]                    datasets/kitti360_im_simultenous_densification.py:186-203
  *   sdp_view_finalize      __getitem__ post-processing of the range images  datasets/kitti360_im_8Batch.py:221-304
@@ -233,6 +235,40 @@ int sdp_range_project_workspace_size(int H, int W, size_t* bytes);
 int sdp_range_project(const double* points, int N, int stride, int has_intensity, const double* origin,
                       int H, int W, double* depth, double* intensity, uint8_t* obfuscation, uint8_t* sky,
                       int64_t* index, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- range image -> point cloud (MeasureResults/SceneCompleter.py:43-70, 105-121, 259-264) ----
+ * The inverse of sdp_range_project for the samplers' images: x DEVICE float32 [B][C][H][W]
+ * (channel 0 the log-depth code, channel 1 the intensity; C = 1 or 2) becomes a compacted cloud of
+ * float64 rows (x, y, z, intensity) -- views in order, pixels row-major inside a view: numpy's
+ * cloud[mask] per view, concatenated (SceneCompleter.py:261-264).  Pixel (i, j) lies at distance
+ * rd = f32(2^f32(|code|*6)) - 1 (float32, 2^v rounded once from float64: the merge's convention,
+ * KITTISampling.py:164-166 -- SceneCompleter's float32 np.power is not correctly rounded) in the
+ * direction (cos az cos el, sin az cos el, sin el), el = (H-1-i)*vA + vMin, az = (W-1-j)*hA + hMin,
+ * float64, with the constants of
+ *   SDP_GEOM_DATASET  datasets/lidar_utils.py:100-114 and SceneCompleter.py:57-70 (sdp_range_project;
+ *                     vMin = radians(3 - 28)) -- the images the datasets render and the runners save;
+ *   SDP_GEOM_SAMPLER  models/KITTISampling.py:29-102 (sdp_consistency_merge; vMin =
+ *                     ((H*-25)//28)*vA + vA/2, 0.36 bin above the dataset's).
+ * Placement: origins DEVICE f64 [B][3] added to each point, OR poses DEVICE f64 [B][4][4] row-major
+ * applied as (pose @ [x y z 1])[:3] (products summed left to right, as sdp_view_transform), or both
+ * NULL = the sensor frame.  A pixel is kept iff rd > min_range (float32 compare; a NaN code fails
+ * it) and keep_view[b][i][j] and keep_shared[i][j] (uint8, each optional) are non-zero
+ * (SceneCompleter.py:259-260: existVals, realDistance > 1.5, not sky).
+ * Outputs (DEVICE): points [n][4] (capacity B*H*W rows; rows >= n are not written), pixel (optional
+ * int32 [n], the flat index b*H*W + i*W + j of each row), offsets int64 [B+1] (view b owns rows
+ * [offsets[b], offsets[b+1]); offsets[B] = n).  Three launches (count, scan, scatter) and no
+ * atomics: the rows are bit-identical from run to run.  B * (H*W rounded up to a multiple of
+ * 256) must stay below 2^31.                                                                  */
+enum sdp_unproject_geometry { SDP_GEOM_DATASET = 0, SDP_GEOM_SAMPLER = 1 };
+int sdp_range_unproject_workspace_size(int B, int H, int W, size_t* bytes);
+int sdp_range_unproject(const float* x, int B, int C, int H, int W, int geometry,
+                        const double* origins, const double* poses,
+                        const uint8_t* keep_view   /* [B][H][W] or NULL */,
+                        const uint8_t* keep_shared /* [H][W]    or NULL */,
+                        float min_range,
+                        double* points /* capacity B*H*W rows of 4 */, int32_t* pixel /* or NULL */,
+                        int64_t* offsets /* [B+1] */,
+                        void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- KITTI-360 view rendering (the datasets' __getitem__) --------------
  * sdp_view_transform: points DEVICE float32 [n][4] (x, y, z, intensity, the .bin layout);

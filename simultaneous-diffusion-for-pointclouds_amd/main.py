@@ -11,7 +11,9 @@ sends them to the Completion runner, which crashes silently, SURVEY Appendix B.6
 errors propagate with a non-zero exit status instead of being logged and swallowed.
 Extra flags: --ckpt (LiDARGen checkpoint; default the reference's path, else synthetic
 weights), --precision {fp32x3,fp32,bf16}, --num_batches (sampling batches; training batches per
-epoch), --n_iters / --snapshot_freq / --max_epochs (override the config's training schedule).
+epoch), --n_iters / --snapshot_freq / --max_epochs (override the config's training schedule),
+--save_clouds (sampling: also write each sampled doThis as a fused point cloud, {doThis}_{saveNum}_Cloud_{ckpt}.npy
+and ..._CloudOffsets_{ckpt}.npy; without it the written files are unchanged).
 """
 import argparse
 import logging
@@ -63,6 +65,10 @@ def parse_args_and_config(argv=None):
     p.add_argument("--kitti_root", type=str, default=None,
                    help="KITTI-360 root (the reference's /data/KITTI-360); views rendered on the GPU "
                         "(sdp.kitti360). Without it the procedural scene of sdp.synthetic is used.")
+    p.add_argument("--save_clouds", action="store_true", default=False,
+                   help="sampling: also unproject every sampled doThis into one fused point cloud on the GPU "
+                        "(sdp.pointcloud): {doThis}_{saveNum}_Cloud_{ckpt}.npy float64 [n,4] and "
+                        "..._CloudOffsets_{ckpt}.npy int64 [views+1]")
     args = p.parse_args(argv)
     args.log_path = os.path.join(args.exp, "logs", args.doc)
     path = args.config if os.path.exists(args.config) else os.path.join("configs", args.config)

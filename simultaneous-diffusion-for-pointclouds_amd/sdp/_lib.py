@@ -68,6 +68,8 @@ _SIGS = {
     "sdp_optim_ema_step": (I, [I, P, P, P, P, P, P, SZ, D, D, D, D, D, I, D, P]),
     "sdp_range_project_workspace_size": (I, [I, I, C.POINTER(SZ)]),
     "sdp_range_project": (I, [P, I, I, I, P, I, I, P, P, P, P, P, P, SZ, P]),
+    "sdp_range_unproject_workspace_size": (I, [I, I, I, C.POINTER(SZ)]),
+    "sdp_range_unproject": (I, [P, I, I, I, I, I, P, P, P, P, F, P, P, P, P, SZ, P]),
     "sdp_view_transform": (I, [P, C.c_int64, P, P, P, P]),
     "sdp_view_gather": (I, [P, I, I, I, P, P, P, P]),
     "sdp_view_finalize": (I, [P, P, P, P, P, P, I, I, I, I, I, I, P, P, P, P, P]),

@@ -13,6 +13,8 @@ as the reference names them (np.save appends .npy):
   {doThis}_{saveNum}_Shared_completion_initial{ckpt}.pth.npy (AllForOne runner only)
 Images are saved as inverse_data_transform (clamp [0,1], datasets/__init__.py:206-215) and
 transposed to [2B',3,H,W] (rows [0,B') depth, [B',2B') intensity, 3 identical channels).
+With ``args.save_clouds`` every sampled doThis also writes its views as one fused point cloud
+(``_save_clouds``): {doThis}_{saveNum}_Cloud_{ckpt}.npy and {doThis}_{saveNum}_CloudOffsets_{ckpt}.npy.
 
 Data: with ``args.kitti_root`` the views come from the KITTI-360 datasets of sdp.kitti360
 (rendered on the GPU) in the order of the reference's MySampler over the pose file
@@ -177,6 +179,43 @@ class Runner:
         torch.distributed.all_gather_object(objs, None if t is None else t.numpy())
         return torch.from_numpy(np.concatenate([o for o in objs if o is not None]))
 
+    def _save_clouds(self, stem, ck, sample, notsky, origins=None, poses=None):
+        """--save_clouds: the sampled views of one doThis as a fused cloud, the offline step of
+        MeasureResults/SceneCompleter.py:43-121, 259-264 on the GPU (sdp.pointcloud).  ``sample`` is the
+        clamped inverse_data_transform image [n,C,H,W] that Masked_completion holds, unprojected with
+        the dataset geometry; a pixel is kept iff it lies in the exist mask, is not sky (``notsky``
+        [n,H,W], True = keep: every dataset here returns logical_not(sky)) and is farther than 1.5 m.
+        Writes {stem}_Cloud_{ck}.npy, float64 [rows,4] (x, y, z, intensity), and
+        {stem}_CloudOffsets_{ck}.npy, int64 [n+1]: view v owns rows offsets[v]:offsets[v+1]."""
+        from .pointcloud import range_image_to_point_cloud
+        n, _, H, W = sample.shape
+        d = self.device
+        f64 = lambda t: None if t is None else t.to(d, torch.float64).contiguous()
+        pts, off = range_image_to_point_cloud(
+            sample.to(d, torch.float32), origins=f64(origins), poses=f64(poses),
+            keep=notsky.reshape(n, H, W).to(d), exist=torch.from_numpy(synthetic.exist_mask(H, W)).to(d),
+            min_range=1.5, geometry="dataset")
+        np.save(os.path.join(self.args.image_folder, f"{stem}_Cloud_{ck}.npy"), pts.cpu().numpy())
+        np.save(os.path.join(self.args.image_folder, f"{stem}_CloudOffsets_{ck}.npy"), off.cpu().numpy())
+
+    def _cloud_poses(self, toWorld, k, kitti):
+        """Sensor -> world matrix of every sampled view ([n,4,4] float64; k = views kept per megabatch), so
+        that the cloud lies in the world frame of the saved toWorld_*.npy.
+          * KITTI360_im_8batch: the view is rendered from the origin of its own goal pose: toWorld.
+          * KITTI360_im_AllForOne / _simultaneous_densification from --kitti_root: every view of a megabatch
+            shares one pose frame (the same toWorld) and view j of the megabatch is rendered from
+            data.modifications[j] inside it (sdp/kitti360.py render): toWorld @ translate(modifications[j]).
+          * the procedural source (no --kitti_root) renders view j from the origin of a pose of its own,
+            translated 5 j metres (sdp.synthetic.scene_views), whatever the dataset: toWorld."""
+        n = toWorld.shape[0]
+        poses = toWorld.reshape(n, 4, 4).to(torch.float64)
+        if kitti or not getattr(self.args, "kitti_root", None):
+            return poses
+        mods = np.asarray(self.config.data.modifications, dtype=np.float64)
+        shift = torch.eye(4, dtype=torch.float64).repeat(n, 1, 1)
+        shift[:, :3, 3] = torch.from_numpy(mods[np.arange(n) % k])
+        return poses @ shift
+
     def sample(self):
         if self.config.data.dataset == "kitti360_im_SceneCompletion":
             return self.sample_completion()
@@ -284,6 +323,8 @@ class Runner:
                     self._png(to_grid_layout(shared), f"{do}_{png_id}_Shared_image_grid_initial{ck}.png", nrow)
                     np.save(os.path.join(folder, f"{do}_{save_num}_Shared_completion_initial{ck}.pth"),
                             to_grid_layout(shared).numpy())
+                if getattr(self.args, "save_clouds", False):
+                    self._save_clouds(f"{do}_{save_num}", ck, sample, sky, poses=self._cloud_poses(toWorld, k, kitti))
 
     # ------------------------------------------------------------------------------ scene completion
     def _completion_source(self, B, aB, H, W):
@@ -318,7 +359,10 @@ class Runner:
         per-view origins (startStep 2, setting 7, correlation 0.01, grad_ref 1, Completion:548-566)
         and saves TimeTaken, the Masked and the Shared (last merge) images.  Quirks kept: the
         dataset's mask (True = known after logical_not) multiplies the input as in the reference,
-        TimeTaken starts at 999999 (L512), the Shared files are named by the batch counter."""
+        TimeTaken starts at 999999 (L512), the Shared files are named by the batch counter.
+        With --save_clouds the cloud of doThis 1 is placed with the per-view origins the dataset
+        projected with, i.e. in the recentred frame sdp/completion.py projects in; adding the raw
+        scan's median back (SceneCompleter.py:105-112) stays with the consumer."""
         c = self.config
         rank, world = _dist()
         B, aB = c.sampling.batch_size, c.sampling.actualBatchSize
@@ -377,6 +421,9 @@ class Runner:
                 np.save(os.path.join(folder, f"{do}_{save_num}_Masked_completion_{ck}.pth"), sample.numpy())
                 self._png(initial, f"{do}_{bi}_Shared_image_grid_initial{ck}.png", nrow)
                 np.save(os.path.join(folder, f"{do}_{bi}_Shared_completion_initial{ck}.pth"), initial.numpy())
+                if getattr(self.args, "save_clouds", False):
+                    self._save_clouds(f"{do}_{save_num}", ck,
+                                      inverse_data_transform(final.view(B, c.data.channels, H, W)), sky_full, origins=mods)
 
     # ------------------------------------------------------------------------------ training
     def _train_source(self, Bt, rank, world):
