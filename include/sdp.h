@@ -28,8 +28,9 @@
  *   sdp_view_transform     pose chain fromWorld @ (toWorld @ p)             datasets/kitti360_im_8Batch.py:146-190
  *   sdp_view_gather        scanPoints[index[index >= 0]]                    datasets/kitti360_im_simultenous_densification.py:186-203
  *   sdp_view_finalize      __getitem__ post-processing of the range images  datasets/kitti360_im_8Batch.py:221-304
- *   sdp_grid_subsample     voxel-grid subsampling (HOST)                    datasets/cpp_wrappers/cpp_subsampling/
+ *   sdp_grid_subsample     voxel-grid subsampling, HOST memory, both methods   datasets/cpp_wrappers/cpp_subsampling/
  *                                                                             grid_subsampling{,_lidar}.cpp, wrapper.cpp:58-285
+ *   sdp_voxel_grid         voxel-grid subsampling, DEVICE memory, barycenters  .../grid_subsampling/grid_subsampling.cpp:46-102
  */
 #ifndef SDP_H
 #define SDP_H
@@ -298,7 +299,8 @@ int sdp_view_finalize(const double* depth, const double* intensity, const uint8_
                       int variant, int first_view, double* real, uint8_t* notmask, uint8_t* notsky, double* goal,
                       void* stream);
 
-/* ---- §8(f)-3: voxel-grid subsampling, HOST memory (no stream) ------------------------------
+/* ---- §8(f)-3: voxel-grid subsampling: sdp_grid_subsample on HOST memory (no stream), sdp_voxel_grid
+ * on DEVICE memory (below) ----------------------------------------------------------------------
  * sdp_grid_subsample replaces the CPython modules grid_subsampling.compute (method 0,
  *   "barycenters": grid_subsampling.cpp:46-102) and grid_subsampling_lidar.compute (method 1:
  *   grid_subsampling_lidar.cpp:46-120), wrapper.cpp:58-285.  points float32 [n][3], features
@@ -308,6 +310,33 @@ int sdp_view_finalize(const double* depth, const double* intensity, const uint8_
 int sdp_grid_subsample(const float* points, int64_t n, const float* features, int fdim, const int32_t* classes,
                        int ldim, float sample_dl, int method, float* out_points, float* out_features,
                        int32_t* out_classes, int64_t* out_n);
+
+/* ---- voxel-grid subsampling on the DEVICE (method 0, "barycenters": grid_subsampling.cpp:46-102) ----
+ * The same float32 arithmetic in the same order as sdp_grid_subsample with method 0, so every output
+ * bit equals the host's; the rows come in ASCENDING VOXEL KEY (the host returns std::unordered_map
+ * order: the two agree as sets), and a majority label with equal votes is the SMALLEST label value (the
+ * host keeps the first maximum in hash order).  Inputs (DEVICE): points float32 [n][stride], stride 3
+ * or 4, xyz first; features float32 [n][fdim] or NULL; classes int32 [n][ldim] or NULL.  A point with a
+ * non-finite coordinate is skipped everywhere: no key, no vote, inverse = -1.  Outputs (DEVICE, capacity
+ * n rows each; rows >= m are not written): out_points [m][3], out_features [m][fdim], out_classes
+ * [m][ldim]; optional (NULL = skip) out_keys int64 [m] (ix + nx*iy + nx*ny*iz), out_counts int32 [m],
+ * out_order int32 [points used] (the stable key-sorted permutation of the used point indices),
+ * out_inverse int32 [n] (the output row of every point).  info int64 [5] = {m, nx, ny, nz, points used}:
+ * m = 0 when no point is finite; m = -1 when the grid has more than 2^40 cells (nx*ny*nz > 2^40) --
+ * then nothing but info is written.  Count / scan / scatter passes on `stream` (a stable 8-bit radix
+ * sort of (key, point index), segment heads, per-voxel sums in ascending point index), no host
+ * synchronisation, no floating-point atomics: bit-identical from run to run.  Point indices and rows
+ * are int32: 1 <= n <= 2^30.  workspace: 16-byte aligned, sdp_voxel_grid_workspace_size(n) bytes.   */
+int sdp_voxel_grid_workspace_size(int64_t n, size_t* bytes);
+int sdp_voxel_grid(const float* points, int64_t n, int stride, const float* features, int fdim, const int32_t* classes,
+                   int ldim, float sample_dl, float* out_points, float* out_features, int32_t* out_classes,
+                   int64_t* out_keys /* or NULL */, int32_t* out_counts /* or NULL */, int32_t* out_order /* or NULL */,
+                   int32_t* out_inverse /* or NULL */, int64_t* info /* [5] */,
+                   void* workspace, size_t workspace_bytes, void* stream);
+/* Measurement hook (tools/voxel_bench.py): events = HOST array of 7 hipEvent_t that every later
+ * sdp_voxel_grid of this thread records on its stream -- before the first kernel, then after the bounds,
+ * the keys, the sort, the segment heads, the reduction and the labels (+ info); NULL switches it off.   */
+int sdp_voxel_grid_stage_events(void* const* events);
 
 #ifdef __cplusplus
 }

@@ -13,7 +13,8 @@ Extra flags: --ckpt (LiDARGen checkpoint; default the reference's path, else syn
 weights), --precision {fp32x3,fp32,bf16}, --num_batches (sampling batches; training batches per
 epoch), --n_iters / --snapshot_freq / --max_epochs (override the config's training schedule),
 --save_clouds (sampling: also write each sampled doThis as a fused point cloud, {doThis}_{saveNum}_Cloud_{ckpt}.npy
-and ..._CloudOffsets_{ckpt}.npy; without it the written files are unchanged).
+and ..._CloudOffsets_{ckpt}.npy; without it the written files are unchanged),
+--cloud_grid DL (with --save_clouds: also write that cloud on a voxel grid of DL metres, ..._CloudGrid_{ckpt}.npy).
 """
 import argparse
 import logging
@@ -69,6 +70,10 @@ def parse_args_and_config(argv=None):
                    help="sampling: also unproject every sampled doThis into one fused point cloud on the GPU "
                         "(sdp.pointcloud): {doThis}_{saveNum}_Cloud_{ckpt}.npy float64 [n,4] and "
                         "..._CloudOffsets_{ckpt}.npy int64 [views+1]")
+    p.add_argument("--cloud_grid", type=float, default=None, metavar="DL",
+                   help="with --save_clouds: also voxel-grid subsample each fused cloud on the GPU "
+                        "(sdp.pointcloud.voxel_grid_subsample) with voxels of DL metres: "
+                        "{doThis}_{saveNum}_CloudGrid_{ckpt}.npy float64 [m,4], barycentre and mean intensity")
     args = p.parse_args(argv)
     args.log_path = os.path.join(args.exp, "logs", args.doc)
     path = args.config if os.path.exists(args.config) else os.path.join("configs", args.config)

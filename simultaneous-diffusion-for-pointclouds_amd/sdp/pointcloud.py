@@ -16,6 +16,11 @@ Two vertical origins exist in the reference and they are NOT interchangeable:
                       images the datasets render and the runners save (``sdp_range_project``);
   geometry="sampler"  vMin = ((H*-25)//28)*vA + vA/2    KITTISampling.py:29-102 -- the grid the
                       consistency merge reprojects in, 0.36 bin (0.16 degrees) above the dataset's.
+
+``voxel_grid_subsample`` puts such a cloud on a voxel grid without leaving the device
+(``sdp_voxel_grid``, csrc/voxel_grid.hip): the barycentre, the mean features and the majority labels
+of every occupied voxel, bit for bit what ``sdp.grid_subsampling.compute`` gives on the host, in
+ascending voxel key.
 """
 from __future__ import annotations
 
@@ -78,9 +83,93 @@ def range_image_to_point_cloud(x, origins=None, poses=None, keep=None, exist=Non
     return points[:total], offsets
 
 
-def fuse_views(x, origins=None, poses=None, keep=None, exist=None, min_range=1.5, geometry="dataset"):
-    """The views of one scan as a single cloud [n,4] (SceneCompleter.py:261-264)."""
-    return range_image_to_point_cloud(x, origins, poses, keep, exist, min_range, geometry)[0]
+def voxel_grid_subsample(points, features=None, classes=None, sampleDl=0.1, center=None,
+                         return_keys=False, return_counts=False, return_inverse=False):
+    """Voxel-grid subsampling on the device (method "barycenters" of grid_subsampling.compute).
+
+    points: cuda [n,3] or [n,4] (xyz first), float32 or float64; features: cuda float [n,d] or None;
+    classes: cuda integer [n] or [n,l] or None.  With float32 points the result is float32, bit-equal to
+    ``sdp.grid_subsampling.compute`` on the same arrays.  With float64 points the grid runs on
+    q = float32(p - center) and the barycentres come back as float64(barycentre) + center; center is
+    float64 [3] and defaults to zeros.  A point with a non-finite coordinate is skipped.
+
+    Returns the points [m,3] alone, or a tuple in the order points, features [m,d], classes [m,l], then
+    the requested extras: keys int64 [m] (ascending: the row order), counts int32 [m], inverse int32 [n]
+    (the row of every point, -1 for a skipped one).  One host sync, to read m.  Labels with equal votes
+    resolve to the smallest label value.  Raises RuntimeError when the grid exceeds 2^40 cells."""
+    if not torch.is_tensor(points) or not points.is_cuda or points.dim() != 2 or points.shape[1] not in (3, 4):
+        raise ValueError("voxel_grid_subsample expects a cuda [n,3] or [n,4] tensor of points")
+    if points.dtype not in (torch.float32, torch.float64):
+        raise ValueError("points must be float32 or float64")
+    dev = points.device
+    n = points.shape[0]
+    wide = points.dtype == torch.float64
+    if center is not None and not wide:
+        raise ValueError("center applies to float64 points only")
+    if wide:
+        c64 = torch.zeros(3, dtype=torch.float64, device=dev) if center is None else \
+            torch.as_tensor(center, dtype=torch.float64).to(dev).reshape(3)
+        pts = (points[:, :3] - c64).to(torch.float32).contiguous()
+    else:
+        pts = points.contiguous()
+    f = c = None
+    fdim = ldim = 0
+    if features is not None:
+        if not features.is_cuda or features.dim() != 2 or features.shape[0] != n or features.shape[1] < 1:
+            raise ValueError("features must be a cuda [n,d] tensor")
+        f = features.to(torch.float32).contiguous()
+        fdim = f.shape[1]
+    if classes is not None:
+        if not classes.is_cuda or classes.dim() not in (1, 2) or classes.shape[0] != n:
+            raise ValueError("classes must be a cuda [n] or [n,l] tensor")
+        c = classes.reshape(n, -1).to(torch.int32).contiguous()
+        ldim = c.shape[1]
+    L = _lib.lib()
+    nb = _lib.SZ()
+    _lib.check(L.sdp_voxel_grid_workspace_size(n, _lib.C.byref(nb)), "voxel_grid_ws")
+    with torch.cuda.device(dev):
+        ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+        op = torch.empty(n, 3, dtype=torch.float32, device=dev)
+        of = torch.empty(n, fdim, dtype=torch.float32, device=dev) if f is not None else None
+        oc = torch.empty(n, ldim, dtype=torch.int32, device=dev) if c is not None else None
+        keys = torch.empty(n, dtype=torch.int64, device=dev) if return_keys else None
+        counts = torch.empty(n, dtype=torch.int32, device=dev) if return_counts else None
+        inverse = torch.empty(n, dtype=torch.int32, device=dev) if return_inverse else None
+        info = torch.empty(5, dtype=torch.int64, device=dev)
+        _lib.check(L.sdp_voxel_grid(pts.data_ptr(), n, pts.shape[1], _lib.ptr(f), fdim, _lib.ptr(c), ldim,
+                                    float(np.float32(sampleDl)), op.data_ptr(), _lib.ptr(of), _lib.ptr(oc),
+                                    _lib.ptr(keys), _lib.ptr(counts), None, _lib.ptr(inverse), info.data_ptr(),
+                                    ws.data_ptr(), ws.numel(), _lib.stream()), "voxel_grid")
+        m, nx, ny, nz, _ = (int(v) for v in info.tolist())
+    if m < 0:
+        raise RuntimeError(f"voxel_grid_subsample: a grid of {nx} x {ny} x {nz} cells at sampleDl = {sampleDl} "
+                           "exceeds 2^40 cells")
+    out = [op[:m].to(torch.float64) + c64 if wide else op[:m]]
+    if of is not None:
+        out.append(of[:m])
+    if oc is not None:
+        out.append(oc[:m])
+    if return_keys:
+        out.append(keys[:m])
+    if return_counts:
+        out.append(counts[:m])
+    if return_inverse:
+        out.append(inverse)
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+def fuse_views(x, origins=None, poses=None, keep=None, exist=None, min_range=1.5, geometry="dataset",
+               grid=None, center=None):
+    """The views of one scan as a single cloud [n,4] (SceneCompleter.py:261-264).  With grid=dl the cloud
+    is put on a voxel grid of that size (``voxel_grid_subsample`` around ``center``): [m,4] float64, the
+    barycentre and the mean intensity of every occupied voxel."""
+    cloud = range_image_to_point_cloud(x, origins, poses, keep, exist, min_range, geometry)[0]
+    if grid is None:
+        return cloud
+    if cloud.shape[0] == 0:
+        return cloud
+    pts, inten = voxel_grid_subsample(cloud[:, :3], features=cloud[:, 3:4], sampleDl=grid, center=center)
+    return torch.cat((pts, inten.to(torch.float64)), 1)
 
 
 def write_bin(path, points) -> None:

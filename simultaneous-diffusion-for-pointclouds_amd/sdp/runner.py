@@ -14,7 +14,8 @@ as the reference names them (np.save appends .npy):
 Images are saved as inverse_data_transform (clamp [0,1], datasets/__init__.py:206-215) and
 transposed to [2B',3,H,W] (rows [0,B') depth, [B',2B') intensity, 3 identical channels).
 With ``args.save_clouds`` every sampled doThis also writes its views as one fused point cloud
-(``_save_clouds``): {doThis}_{saveNum}_Cloud_{ckpt}.npy and {doThis}_{saveNum}_CloudOffsets_{ckpt}.npy.
+(``_save_clouds``): {doThis}_{saveNum}_Cloud_{ckpt}.npy and {doThis}_{saveNum}_CloudOffsets_{ckpt}.npy;
+with ``args.cloud_grid`` = DL besides them {doThis}_{saveNum}_CloudGrid_{ckpt}.npy, that cloud on a voxel grid of DL metres.
 
 Data: with ``args.kitti_root`` the views come from the KITTI-360 datasets of sdp.kitti360
 (rendered on the GPU) in the order of the reference's MySampler over the pose file
@@ -186,8 +187,12 @@ class Runner:
         the dataset geometry; a pixel is kept iff it lies in the exist mask, is not sky (``notsky``
         [n,H,W], True = keep: every dataset here returns logical_not(sky)) and is farther than 1.5 m.
         Writes {stem}_Cloud_{ck}.npy, float64 [rows,4] (x, y, z, intensity), and
-        {stem}_CloudOffsets_{ck}.npy, int64 [n+1]: view v owns rows offsets[v]:offsets[v+1]."""
-        from .pointcloud import range_image_to_point_cloud
+        {stem}_CloudOffsets_{ck}.npy, int64 [n+1]: view v owns rows offsets[v]:offsets[v+1].
+        With --cloud_grid DL also {stem}_CloudGrid_{ck}.npy, float64 [m,4]: the barycentre and the mean
+        intensity of every occupied DL-metre voxel of that cloud (sdp.pointcloud.voxel_grid_subsample), in
+        ascending voxel key, the float32 grid centred on the translation of the first view's pose or
+        origin (zeros without either)."""
+        from .pointcloud import range_image_to_point_cloud, voxel_grid_subsample
         n, _, H, W = sample.shape
         d = self.device
         f64 = lambda t: None if t is None else t.to(d, torch.float64).contiguous()
@@ -197,6 +202,19 @@ class Runner:
             min_range=1.5, geometry="dataset")
         np.save(os.path.join(self.args.image_folder, f"{stem}_Cloud_{ck}.npy"), pts.cpu().numpy())
         np.save(os.path.join(self.args.image_folder, f"{stem}_CloudOffsets_{ck}.npy"), off.cpu().numpy())
+        dl = getattr(self.args, "cloud_grid", None)
+        if dl:
+            center = torch.zeros(3, dtype=torch.float64, device=d)
+            if origins is not None:
+                center = f64(origins).reshape(n, 3)[0]
+            elif poses is not None:
+                center = f64(poses).reshape(n, 4, 4)[0, :3, 3]
+            if pts.shape[0]:
+                gp, gi = voxel_grid_subsample(pts[:, :3], features=pts[:, 3:4], sampleDl=float(dl), center=center)
+                grid = torch.cat((gp, gi.to(torch.float64)), 1)
+            else:
+                grid = pts
+            np.save(os.path.join(self.args.image_folder, f"{stem}_CloudGrid_{ck}.npy"), grid.cpu().numpy())
 
     def _cloud_poses(self, toWorld, k, kitti):
         """Sensor -> world matrix of every sampled view ([n,4,4] float64; k = views kept per megabatch), so
