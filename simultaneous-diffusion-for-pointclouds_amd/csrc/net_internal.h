@@ -134,29 +134,33 @@ struct sdp_net {
     for (auto& kv : host) {
       if (!is_conv_w(kv.first)) continue;
       const auto& s = kv.second.shape;
-      // packings: 0 = forward "#frag" (32x32 fragment order: the exact-fp32 forward), 3 = the forward in
-      // 16x16 fragment order "#frag16" (bf16 modes), 4 = the data gradient in 16x16 fragment order
-      // "#dfrag16" (training: bf16 modes); (1 was the data gradient in 32x32 order -- read in 16-B pieces
-      // at a 64-B lane stride, and in bf16 mode only the hi half of each 32 B: replaced in round 6 --
-      // 2 the Winograd packing, removed with its kernel)
-      // 5 = "#pool4x4": the 3x3 of a ConvMeanPool merged with its 2x2 mean into a 4x4 stride-2 conv, 16 taps in
-      // 16x16 fragment order (the sampling forward, bf16 modes; train_aux.hip pack_slot16p)
-      for (int dg = 0; dg < 6; ++dg) {
-        if (dg == 0 && mode != sdp::MODE_F32) continue;
-        if (dg == 1 || dg == 2) continue;
-        if (dg == 3 && mode == sdp::MODE_F32) continue;
-        if (dg == 4 && (!train_packs || mode == sdp::MODE_F32)) continue;
-        if (dg == 5 && (mode == sdp::MODE_F32 || !is_pool3x3_w(kv.first))) continue;
-        const std::string fk = kv.first + (dg == 0 ? "#frag" : dg == 3 ? "#frag16" : dg == 4 ? "#dfrag16" : "#pool4x4");
-        const int nt = dg == 5 ? 16 : (int)(s[2] * s[3]);
-        const size_t n = (size_t)s[0] * s[1] * nt;
+      // the packings of one conv weight, in descriptor order; `dgrad` is the layout's id in the pack kernel
+      // (train_aux.hip; ids 1 and 2 are retired)
+      const bool f32 = mode == sdp::MODE_F32;
+      const int taps = (int)(s[2] * s[3]);
+      const struct {
+        const char* suffix;
+        int dgrad, taps;
+        bool build;
+      } packings[] = {
+          {"#frag", 0, taps, f32},                                 // forward, 32x32 fragment order: exact fp32
+          {"#frag16", 3, taps, !f32},                              // forward, 16x16 fragment order: bf16 modes
+          {"#dfrag16", 4, taps, !f32 && train_packs},              // data gradient, 16x16 fragment order: training
+          // the 3x3 of a ConvMeanPool merged with its 2x2 mean into a 4x4 stride-2 conv, 16 taps in 16x16
+          // fragment order (the sampling forward, bf16 modes; train_aux.hip pack_slot16p)
+          {"#pool4x4", 5, 16, !f32 && is_pool3x3_w(kv.first)},
+      };
+      for (const auto& pk : packings) {
+        if (!pk.build) continue;
+        const std::string fk = kv.first + pk.suffix;
+        const size_t n = (size_t)s[0] * s[1] * pk.taps;
         if (!dev.count(fk)) {
           void* p = nullptr;
           sdp::chk(hipMalloc(&p, n * 4), "hipMalloc");
           dev[fk] = p;
         }
-        d.push_back(sdp::PackDesc{P(kv.first), reinterpret_cast<uint32_t*>(dev[fk]), (int)s[0], (int)s[1], nt, dg,
-                                  total});
+        d.push_back(sdp::PackDesc{P(kv.first), reinterpret_cast<uint32_t*>(dev[fk]), (int)s[0], (int)s[1], pk.taps,
+                                  pk.dgrad, total});
         total += n;
       }
     }

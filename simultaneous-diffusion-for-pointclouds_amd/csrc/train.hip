@@ -7,9 +7,10 @@
 //   sdp_dsm_loss          : anneal_dsm_score_estimation_with_mask (losses/dsm.py:67-119)
 //   sdp_adam_ema_step     : optimizer.step() of torch.optim.Adam + EMAHelper.update (ema.py:16-21)
 //
-// The forward mirrors net.hip's fused plan (InstanceNorm++ statistics in conv epilogues, its
-// affine + ELU in the consumer's prologue, residual / upsample / CRP sums as epilogues) but
-// keeps its tensors.  The backward walks the graph in reverse with
+// The forward is the fused plan of net_graph.h (InstanceNorm++ statistics in conv epilogues, its
+// affine + ELU in the consumer's prologue, residual / upsample / CRP sums as epilogues), the same
+// walker the sampling forward runs, on a runtime that keeps its tensors.  The backward walks the
+// graph in reverse with
 //   data gradients  : conv_mfma_kernel on dy with flipped/transposed weights (conv_bwd.hip),
 //                     fusing elu' and residual gradients into its epilogue,
 //   weight gradients: conv_wgrad_kernel (wgrad.hip, MFMA with LDS transpose reads),
@@ -20,16 +21,13 @@
 #include <set>
 #include <string>
 
-#include "net_internal.h"
+#include "net_graph.h"
 
 namespace sdp {
 
 // an NHWC activation / gradient tensor of the tape: float32, or bf16 elements when the plan's h16 is set
 // (p is then reinterpreted by the kernels: every launch below passes h16 along)
-struct T4 {
-  float* p;
-  int H, W, C;
-};
+using T4 = Act;
 
 struct TrainPlan {
   sdp_net* net = nullptr;
@@ -47,7 +45,7 @@ struct TrainPlan {
   std::map<std::string, float*> fl;   // saved per-norm tables: "<key>#ss", "<key>#nst"
   std::map<std::string, uint8_t*> idxs;  // saved maxpool argmax indices
   float* stats = nullptr;
-  float* mvs = nullptr;               // inpp_finalize scratch
+  float* mv = nullptr;                // inpp_finalize scratch
   float* xin = nullptr;               // copy of the forward input [B,2,H,W]
   int64_t* lab = nullptr;             // copy of the labels
   // backward scratch
@@ -94,7 +92,6 @@ struct TrainPlan {
     if (it == fl.end()) throw std::runtime_error("tape: missing " + k);
     return it->second;
   }
-  int ks_of(const std::string& wkey) const { return (int)net->host.at(wkey + ".weight").shape[2]; }
   // the gradients of `keys` are final once the launches enqueued so far have run.  The final prefix
   // advances only over layout entries that are ALL finished, in arena order: a parameter finished
   // out of layout order (e.g. a key-ordered fallback layout) never lets a bucket event fire over a
@@ -115,186 +112,30 @@ struct TrainPlan {
       ok(hipEventRecord(bucket_ev[next_bucket++], st), "hipEventRecord (gradient bucket)");
   }
 
-  // ------------------------------------------------------------------ forward pieces
-  struct Opt {
-    int pro = PRO_NONE;
-    const float* ss = nullptr;
-    bool bias = true;
-    const float* res = nullptr;
-    const float* up = nullptr;
-    float* out2 = nullptr;
-    const float* res2 = nullptr;
-    bool epi_elu = false;
-    bool stats = false;
-    int dil = 1;
-    bool circular = true;
-    bool pool = false;
-  };
-  void conv(const T4& in, const std::string& wkey, const T4& out, const Opt& o) {
-    const auto& hp = net->host.at(wkey + ".weight");
-    if ((int)hp.shape[1] != in.C || (int)hp.shape[0] != out.C) throw std::runtime_error("conv shape mismatch " + wkey);
-    if (dry) return;
-    ConvArgs a{};
-    a.in = in.p;
-    a.wf = net->mode == MODE_F32 ? reinterpret_cast<const uint4*>(P(wkey + ".weight#frag")) : nullptr;
-    a.wf16 = net->mode == MODE_F32 ? nullptr : reinterpret_cast<const uint4*>(P(wkey + ".weight#frag16"));
-    a.bias = o.bias ? P(wkey + ".bias") : nullptr;
-    a.out = out.p;
-    a.res = o.res;
-    a.out2 = o.out2;
-    a.res2 = o.res2;
-    a.up = o.up;
-    a.pro_ss = o.pro == PRO_AFFINE_ELU ? o.ss : P("#ident_ss");
-    a.ss_bstride = o.pro == PRO_AFFINE_ELU ? 2 * in.C : 0;
-    a.stats = o.stats ? stats : nullptr;
-    a.B = B;
-    a.H = in.H;
-    a.W = in.W;
-    a.Cin = in.C;
-    a.Cout = out.C;
-    a.dil = o.dil;
-    a.circular = o.circular ? 1 : 0;
-    a.pro_mode = o.pro;
-    a.epi_elu = o.epi_elu ? 1 : 0;
-    a.io16 = h16 ? 1 : 0;
-    const char* why = "conv launch";
-    ok(conv_mfma(net->mode, a, (int)hp.shape[2], o.pool, st, &why), std::string(why) + " (" + wkey + ")");
-  }
-  // statistics of the last stats-writing conv -> (scale, shift) + backward statistics of `nkey`
-  void norm(const std::string& nkey, int T, float cnt, int c) {
+  // ------------------------------------------------------------------ forward: the runtime of the graph walker
+  // (net_graph.h).  Bump allocation in walker order, nothing reused; what the backward reads is kept
+  // under string keys in saved / fl / idxs; a dry run launches nothing
+  static constexpr bool kTraining = true;
+  Act alloc(int h, int w, int c) { return mk(h, w, c); }
+  void release(const Act&) {}
+  void keep(const std::string& key, const Act& t) { saved[key] = t; }
+  NormOut norm_out(const std::string& nkey, int c) {
     float* ss = take((size_t)B * c * 2);
     float* nst = take((size_t)B * c * 4);
     fl[nkey + "#ss"] = ss;
     fl[nkey + "#nst"] = nst;
-    if (dry) return;
-    ok(inpp_finalize(stats, B, T, cnt, c, P(nkey + ".alpha"), P(nkey + ".gamma"), P(nkey + ".beta"), ss, st, nst, mvs),
-       "inpp_finalize " + nkey);
+    return {ss, nst};
   }
-  static int tiles(const T4& t) { return t.H * t.W / 128; }
-
-  // ResidualBlock.forward (layers.py:443-456)
-  T4 resf(const std::string& k, const T4& x, bool down, int dil, int x_tiles, float x_cnt) {
-    saved[k + ".x"] = x;
-    norm(k + ".normalize1", x_tiles, x_cnt, x.C);
-    T4 h1 = like(x);
-    Opt o1;
-    o1.pro = PRO_AFFINE_ELU;
-    o1.ss = F(k + ".normalize1#ss");
-    o1.stats = true;
-    o1.dil = dil;
-    conv(x, k + ".conv1", h1, o1);
-    saved[k + ".h1"] = h1;
-    norm(k + ".normalize2", tiles(h1), 128.f, h1.C);
-    Opt o2;
-    o2.pro = PRO_AFFINE_ELU;
-    o2.ss = F(k + ".normalize2#ss");
-    o2.stats = true;
-    o2.dil = dil;
-    T4 out;
-    if (down && dil == 1) {   // ConvMeanPool conv2 + ConvMeanPool 1x1 shortcut (layers.py:417-420)
-      T4 s = mk(x.H / 2, x.W / 2, 2 * x.C);
-      Opt os;
-      os.circular = false;
-      os.pool = true;
-      conv(x, k + ".shortcut.conv", s, os);
-      out = like(s);
-      o2.circular = false;
-      o2.pool = true;
-      o2.res = s.p;
-      conv(h1, k + ".conv2.conv", out, o2);
-    } else if (down) {         // dilated: no resampling, dilated shortcut (layers.py:411-415)
-      T4 s = like(x);
-      Opt os;
-      os.dil = dil;
-      conv(x, k + ".shortcut", s, os);
-      out = like(x);
-      o2.res = s.p;
-      conv(h1, k + ".conv2", out, o2);
-    } else {
-      out = like(x);
-      o2.res = x.p;
-      conv(h1, k + ".conv2", out, o2);
-    }
-    return out;
+  uint8_t* argmax_out(const std::string& key, size_t n) {
+    return idxs[key] = reinterpret_cast<uint8_t*>(take((n + 3) / 4));   // argmax bytes, in floats
   }
-  // RCUBlock (layers.py:126-134)
-  T4 rcuf(const std::string& k, T4 x, int nb, bool final_elu, bool final_stats) {
-    for (int i = 0; i < nb; ++i) {
-      const std::string c1 = k + "." + std::to_string(i + 1) + "_1_conv", c2 = k + "." + std::to_string(i + 1) + "_2_conv";
-      saved[k + ".x" + std::to_string(i)] = x;
-      T4 t = like(x);
-      Opt a;
-      a.pro = PRO_ELU;
-      a.bias = false;
-      conv(x, c1, t, a);
-      saved[k + ".t" + std::to_string(i)] = t;
-      T4 y = like(x);
-      Opt b;
-      b.pro = PRO_ELU;
-      b.bias = false;
-      b.res = x.p;
-      b.epi_elu = final_elu && i == nb - 1;
-      b.stats = final_stats && i == nb - 1;
-      conv(t, c2, y, b);
-      x = y;
-    }
-    saved[k + ".out"] = x;
-    return x;
+  template <class F>
+  void launch(const char* what, const std::string&, double, F&& f) {
+    if (!dry) ok(f(), what);
   }
-  // CRPBlock (layers.py:76-83) on X = ELU(h)
-  T4 crpf(const std::string& k, const T4& X) {
-    saved[k + ".X"] = X;
-    T4 p1 = like(X), path1 = like(X), x1 = like(X), p2 = like(X), x2 = like(X);
-    const size_t nidx = (n(X) + 3) / 4;                // argmax bytes, in floats
-    uint8_t* i1 = reinterpret_cast<uint8_t*>(take(nidx));
-    uint8_t* i2 = reinterpret_cast<uint8_t*>(take(nidx));
-    idxs[k + ".i1"] = i1;
-    idxs[k + ".i2"] = i2;
-    if (!dry) ok(maxpool5(X.p, p1.p, B, X.H, X.W, X.C, st, i1, h16), "maxpool5");
-    Opt a;
-    a.bias = false;
-    a.out2 = x1.p;
-    a.res2 = X.p;
-    conv(p1, k + ".convs.0", path1, a);
-    if (!dry) ok(maxpool5(path1.p, p2.p, B, X.H, X.W, X.C, st, i2, h16), "maxpool5");
-    Opt b;
-    b.bias = false;
-    b.res = x1.p;
-    conv(p2, k + ".convs.1", x2, b);
-    saved[k + ".p1"] = p1;
-    saved[k + ".path1"] = path1;
-    saved[k + ".p2"] = p2;
-    return x2;
-  }
-  // RefineBlock (layers.py:234-249); MSF (layers.py:179-184) fused with the CRP's input ELU
-  T4 refinef(const std::string& k, const T4& a, const T4* b, int cout, int n_out, bool final_stats) {
-    T4 X;
-    if (!b) {
-      X = rcuf(k + ".adapt_convs.0", a, 2, true, false);
-    } else {
-      T4 hA = rcuf(k + ".adapt_convs.0", a, 2, false, false);
-      T4 hB = rcuf(k + ".adapt_convs.1", *b, 2, false, false);
-      if (hA.H == hB.H) {
-        T4 m0 = mk(hA.H, hA.W, cout);
-        conv(hA, k + ".msf.convs.0", m0, Opt{});
-        X = like(m0);
-        Opt o;
-        o.res = m0.p;
-        o.epi_elu = true;
-        conv(hB, k + ".msf.convs.1", X, o);
-      } else {
-        T4 m1 = mk(hB.H, hB.W, cout);
-        conv(hB, k + ".msf.convs.1", m1, Opt{});
-        X = mk(hA.H, hA.W, cout);
-        Opt o;
-        o.up = m1.p;
-        o.epi_elu = true;
-        conv(hA, k + ".msf.convs.0", X, o);
-      }
-      saved[k + ".msf.X"] = X;
-    }
-    T4 x2 = crpf(k + ".crp", X);
-    return rcuf(k + ".output_convs", x2, n_out, false, final_stats);
+  void launch_conv(const ConvArgs& a, int ks, const ConvOpt& o, const std::string& wkey, const Act&, const Act&) {
+    const char* why = "conv launch";
+    ok(conv_mfma(net->mode, a, ks, o.pool, st, &why), std::string(why) + " (" + wkey + ")");
   }
 
   void forward(const float* x, const int64_t* labels, float* out) {
@@ -309,28 +150,8 @@ struct TrainPlan {
       ok(hipMemcpyAsync(lab, labels, (size_t)B * 8, hipMemcpyDeviceToDevice, st), "copy labels");
     }
     stats = take((size_t)B * (H * W / 64) * 2 * C * 2);
-    mvs = take((size_t)B * 2 * C * 4);
-    T4 x0 = mk(H, W, C);
-    if (!dry)
-      ok(begin_conv(xin, P("begin_conv.weight"), P("begin_conv.bias"), x0.p, stats, B, H, W, st, net->mode, h16),
-         "begin_conv");
-    T4 l1 = resf("res1.0", x0, false, 1, H * W / 64, 64.f);
-    l1 = resf("res1.1", l1, false, 1, tiles(l1), 128.f);
-    T4 l2 = resf("res2.0", l1, true, 1, tiles(l1), 128.f);
-    l2 = resf("res2.1", l2, false, 1, tiles(l1), 32.f);
-    T4 l3 = resf("res3.0", l2, true, 2, tiles(l2), 128.f);
-    l3 = resf("res3.1", l3, false, 2, tiles(l3), 128.f);
-    T4 l4 = resf("res4.0", l3, true, 4, tiles(l3), 128.f);
-    l4 = resf("res4.1", l4, false, 4, tiles(l4), 128.f);
-    T4 r1 = refinef("refine1", l4, nullptr, 2 * C, 1, false);
-    T4 r2 = refinef("refine2", l3, &r1, 2 * C, 1, false);
-    T4 r3 = refinef("refine3", l2, &r2, C, 1, false);
-    T4 o = refinef("refine4", l1, &r3, C, 3, true);
-    norm("normalizer", tiles(o), 128.f, C);
-    if (!dry)
-      ok(end_conv(o.p, F("normalizer#ss"), P("end_conv.weight"), P("end_conv.bias"), P("sigmas"), lab, out, B, H, W, C,
-                  st, nullptr, net->mode, h16),
-         "end_conv");
+    mv = take((size_t)B * 2 * C * 4);
+    NetGraph<TrainPlan>{*this}.forward(xin, lab, out, nullptr);
     fwd_bytes = used;
   }
 
@@ -586,8 +407,6 @@ static size_t train_ws_bytes(sdp_net* net, int B) {
 
 using namespace sdp;
 
-static int tfail(const std::string& m) { return sdp_fail(m); }
-
 static void enable_training(sdp_net* net, hipStream_t st) {
   if (net->mode != MODE_F32X3 && net->mode != MODE_BF16) throw std::runtime_error("training needs fp32x3 or bf16");
   if (!net->train_packs) {
@@ -596,70 +415,17 @@ static void enable_training(sdp_net* net, hipStream_t st) {
   }
 }
 
-extern "C" {
-
-int sdp_net_set_tape(sdp_net* net, int bf16) {
-  if (!net || bf16 < 0 || bf16 > 1) return tfail("sdp_net_set_tape: bad argument");
-  net->tape16 = bf16 != 0;
-  return 0;
-}
-
-int sdp_net_train_workspace_size(sdp_net* net, int B, size_t* bytes) {
-  if (!net || !bytes || B <= 0 || !net->finalized) return tfail("sdp_net_train_workspace_size: bad argument");
-  try {
-    *bytes = train_ws_bytes(net, B);
-  } catch (const std::exception& e) {
-    return tfail(std::string("sdp_net_train_workspace_size: ") + e.what());
-  }
-  return 0;
-}
-
-int sdp_net_forward_train(sdp_net* net, const float* x, const int64_t* labels, float* out, int B, void* ws,
-                          size_t ws_bytes, void* stream) {
-  if (!net || !x || !labels || !out || !ws || B <= 0) return tfail("sdp_net_forward_train: bad argument");
-  if (!net->finalized) return tfail("sdp_net_forward_train: call sdp_net_finalize first");
-  try {
-    const size_t need = train_ws_bytes(net, B);
-    if (ws_bytes < need) return tfail("sdp_net_forward_train: workspace too small");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    enable_training(net, st);
-    TrainPlan* p = plan_for(net, B);
-    p->dry = false;
-    p->st = st;
-    p->base = reinterpret_cast<char*>(ws);
-    p->cap = ws_bytes;
-    p->forward(x, labels, out);
-  } catch (const std::exception& e) {
-    return tfail(std::string("sdp_net_forward_train: ") + e.what());
-  }
-  return 0;
-}
-
-int sdp_net_backward(sdp_net* net, const float* dscore, int B, void* ws, size_t ws_bytes, float* grads, void* stream) {
-  if (!net || !dscore || !ws || !grads || B <= 0) return tfail("sdp_net_backward: bad argument");
-  TrainPlan* p = net->plan;
-  if (!p || p->dry || p->B != B || p->base != ws || p->saved.empty())
-    return tfail("sdp_net_backward: no tape -- call sdp_net_forward_train with this workspace and batch first");
-  try {
-    p->st = reinterpret_cast<hipStream_t>(stream);
-    p->cap = ws_bytes;
-    p->backward(dscore, grads);
-  } catch (const std::exception& e) {
-    return tfail(std::string("sdp_net_backward: ") + e.what());
-  }
-  return 0;
-}
-
-int sdp_net_backward_buckets(sdp_net* net, const float* dscore, int B, void* ws, size_t ws_bytes, float* grads,
-                             int n_buckets, const size_t* bucket_end, void* const* events, void* stream) {
+// sdp_net_backward is sdp_net_backward_buckets with no buckets; `who` prefixes the errors of either
+static int backward_entry(const std::string& who, sdp_net* net, const float* dscore, int B, void* ws, size_t ws_bytes,
+                          float* grads, int n_buckets, const size_t* bucket_end, void* const* events, void* stream) {
   if (!net || !dscore || !ws || !grads || B <= 0 || n_buckets < 0 || (n_buckets && (!bucket_end || !events)))
-    return tfail("sdp_net_backward_buckets: bad argument");
+    return sdp_fail(who + "bad argument");
   for (int i = 0; i < n_buckets; ++i)
     if (!events[i] || (i && bucket_end[i] <= bucket_end[i - 1]) || bucket_end[i] > net->arena_floats)
-      return tfail("sdp_net_backward_buckets: bucket ends must increase within the arena, events non-null");
+      return sdp_fail(who + "bucket ends must increase within the arena, events non-null");
   TrainPlan* p = net->plan;
   if (!p || p->dry || p->B != B || p->base != ws || p->saved.empty())
-    return tfail("sdp_net_backward_buckets: no tape -- call sdp_net_forward_train with this workspace and batch first");
+    return sdp_fail(who + "no tape -- call sdp_net_forward_train with this workspace and batch first");
   try {
     p->st = reinterpret_cast<hipStream_t>(stream);
     p->cap = ws_bytes;
@@ -670,23 +436,72 @@ int sdp_net_backward_buckets(sdp_net* net, const float* dscore, int B, void* ws,
     p->n_buckets = 0;
   } catch (const std::exception& e) {
     p->n_buckets = 0;
-    return tfail(std::string("sdp_net_backward_buckets: ") + e.what());
+    return sdp_fail(who + e.what());
   }
   return 0;
+}
+
+extern "C" {
+
+int sdp_net_set_tape(sdp_net* net, int bf16) {
+  if (!net || bf16 < 0 || bf16 > 1) return sdp_fail("sdp_net_set_tape: bad argument");
+  net->tape16 = bf16 != 0;
+  return 0;
+}
+
+int sdp_net_train_workspace_size(sdp_net* net, int B, size_t* bytes) {
+  if (!net || !bytes || B <= 0 || !net->finalized) return sdp_fail("sdp_net_train_workspace_size: bad argument");
+  try {
+    *bytes = train_ws_bytes(net, B);
+  } catch (const std::exception& e) {
+    return sdp_fail(std::string("sdp_net_train_workspace_size: ") + e.what());
+  }
+  return 0;
+}
+
+int sdp_net_forward_train(sdp_net* net, const float* x, const int64_t* labels, float* out, int B, void* ws,
+                          size_t ws_bytes, void* stream) {
+  if (!net || !x || !labels || !out || !ws || B <= 0) return sdp_fail("sdp_net_forward_train: bad argument");
+  if (!net->finalized) return sdp_fail("sdp_net_forward_train: call sdp_net_finalize first");
+  try {
+    const size_t need = train_ws_bytes(net, B);
+    if (ws_bytes < need) return sdp_fail("sdp_net_forward_train: workspace too small");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    enable_training(net, st);
+    TrainPlan* p = plan_for(net, B);
+    p->dry = false;
+    p->st = st;
+    p->base = reinterpret_cast<char*>(ws);
+    p->cap = ws_bytes;
+    p->forward(x, labels, out);
+  } catch (const std::exception& e) {
+    return sdp_fail(std::string("sdp_net_forward_train: ") + e.what());
+  }
+  return 0;
+}
+
+int sdp_net_backward(sdp_net* net, const float* dscore, int B, void* ws, size_t ws_bytes, float* grads, void* stream) {
+  return backward_entry("sdp_net_backward: ", net, dscore, B, ws, ws_bytes, grads, 0, nullptr, nullptr, stream);
+}
+
+int sdp_net_backward_buckets(sdp_net* net, const float* dscore, int B, void* ws, size_t ws_bytes, float* grads,
+                             int n_buckets, const size_t* bucket_end, void* const* events, void* stream) {
+  return backward_entry("sdp_net_backward_buckets: ", net, dscore, B, ws, ws_bytes, grads, n_buckets, bucket_end, events,
+                        stream);
 }
 
 int sdp_dsm_loss(const float* score, const float* noise, const float* mask, const float* used_sigma, int B, int n_img,
                  float anneal_power, float* dscore, float* loss, float* loss_per, float* part, void* stream) {
   if (!score || !noise || !mask || !used_sigma || !dscore || !loss || !part || B <= 0 || n_img <= 0)
-    return tfail("sdp_dsm_loss: bad argument");
+    return sdp_fail("sdp_dsm_loss: bad argument");
   hipError_t e = dsm_loss(score, noise, mask, used_sigma, B, n_img, anneal_power, dscore, loss, loss_per, part,
                           reinterpret_cast<hipStream_t>(stream));
-  return e == hipSuccess ? 0 : tfail(std::string("sdp_dsm_loss: ") + hipGetErrorString(e));
+  return e == hipSuccess ? 0 : sdp_fail(std::string("sdp_dsm_loss: ") + hipGetErrorString(e));
 }
 
 int sdp_adam_ema_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema_shadow, size_t n,
                       double lr, double beta1, double beta2, double eps, int step, double ema_mu, void* stream) {
-  if (!params || !grads || !exp_avg || !exp_avg_sq || n == 0 || step < 1) return tfail("sdp_adam_ema_step: bad argument");
+  if (!params || !grads || !exp_avg || !exp_avg_sq || n == 0 || step < 1) return sdp_fail("sdp_adam_ema_step: bad argument");
   return sdp_optim_ema_step(SDP_OPTIM_ADAM, params, grads, exp_avg, exp_avg_sq, nullptr, ema_shadow, n, lr, beta1, beta2,
                             eps, 0.0, step, ema_mu, stream);
 }
@@ -696,7 +511,7 @@ int sdp_optim_ema_step(int kind, float* params, const float* grads, float* state
                        double weight_decay, int step, double ema_mu, void* stream) {
   if (!params || !grads || !state0 || n == 0 || step < 1 || kind < SDP_OPTIM_ADAM || kind > SDP_OPTIM_SGD ||
       (kind == SDP_OPTIM_ADAM && !state1))
-    return tfail("sdp_optim_ema_step: bad argument");
+    return sdp_fail("sdp_optim_ema_step: bad argument");
   OptimHyper h{};
   h.b1 = (float)beta1;
   h.b2 = (float)beta2;
@@ -717,7 +532,7 @@ int sdp_optim_ema_step(int kind, float* params, const float* grads, float* state
   hipError_t e = optim_ema(kind, params, grads, state0, kind == SDP_OPTIM_ADAM ? state1 : nullptr,
                            kind == SDP_OPTIM_ADAM ? state2 : nullptr, ema_shadow, n, h,
                            reinterpret_cast<hipStream_t>(stream));
-  return e == hipSuccess ? 0 : tfail(std::string("sdp_optim_ema_step: ") + hipGetErrorString(e));
+  return e == hipSuccess ? 0 : sdp_fail(std::string("sdp_optim_ema_step: ") + hipGetErrorString(e));
 }
 
 }  // extern "C"
