@@ -31,6 +31,8 @@
  *   sdp_grid_subsample     voxel-grid subsampling, HOST memory, both methods   datasets/cpp_wrappers/cpp_subsampling/
  *                                                                             grid_subsampling{,_lidar}.cpp, wrapper.cpp:58-285
  *   sdp_voxel_grid         voxel-grid subsampling, DEVICE memory, barycenters  .../grid_subsampling/grid_subsampling.cpp:46-102
+ *   sdp_cloud_nn           exact nearest neighbour within a radius, cloud to cloud   (no counterpart: MeasureResults/ scores
+ *   sdp_cloud_nn_stats     Chamfer / precision / recall sums of one direction         images only, per-pixel MAE)
  */
 #ifndef SDP_H
 #define SDP_H
@@ -337,6 +339,46 @@ int sdp_voxel_grid(const float* points, int64_t n, int stride, const float* feat
  * sdp_voxel_grid of this thread records on its stream -- before the first kernel, then after the bounds,
  * the keys, the sort, the segment heads, the reduction and the labels (+ info); NULL switches it off.   */
 int sdp_voxel_grid_stage_events(void* const* events);
+
+/* ---- cloud-to-cloud distances on the DEVICE (csrc/cloud_nn.hip) ----
+ * sdp_cloud_nn: for every query point the EXACT nearest target point within max_dist.  Inputs (DEVICE): q
+ * float64 [nq][qstride], t float64 [nt][tstride], xyz first, stride 3 or 4; max_dist R > 0; cell c of the
+ * acceleration grid with R/8 <= c <= R; center float64 [3] or NULL (zeros), finite: the grid runs on
+ * float32(t - center).  Outputs (DEVICE): nn_d2 float64 [nq], nn_idx int32 [nq].
+ *   d2(i,j) = ((qx-tx)*(qx-tx) + (qy-ty)*(qy-ty)) + (qz-tz)*(qz-tz) in float64, every operation rounded once,
+ *   from the ORIGINAL coordinates.  Query i matches j* = argmin_j d2(i,j) over the targets with finite
+ *   coordinates and d2(i,j) <= R*R (the rounded float64 product); among equal d2 the smallest j.  Then
+ *   nn_d2[i] = d2(i,j*), nn_idx[i] = j*; a query without such a target, or with a non-finite coordinate, gets
+ *   +inf and -1.  The result does not depend on cell or center, and two calls give identical bits.
+ * The targets are put on a cell grid with sdp_voxel_grid's machinery (float32 keys, stable radix sort, segment
+ * heads); each query visits the cells around its own in rings of growing Chebyshev distance up to
+ * K = ceil((R + slack) / c), slack = 6 * 2^-23 * (max |float32 target coordinate| + R + 2c) covering every
+ * float32 rounding of the cell assignment, and stops early once no unvisited ring can hold a nearer point
+ * (derivation: the file header).  info int64 [8] = {occupied cells, nx, ny, nz, targets
+ * used, K, brute flag, 0} (brute flag 1: the grid origin rounded above the targets' lower bound on an axis,
+ * the cell keys are unusable and every query scanned all targets -- still exact, O(nq nt)); info[0] = -1 when the grid has more than 2^40 cells and -2 when the slack pushes K
+ * beyond 9 (cell too small for the float32 grid at these coordinates: choose a center near the cloud or a
+ * larger cell) -- then nothing but info is written.  max_dist / cell > 8 fails at the call.  nq = 0 or nt = 0
+ * is valid.  0 <= nq, nt <= 2^30.  No host synchronisation, no floating-point atomics.
+ * workspace: 16-byte aligned, sdp_cloud_nn_workspace_size(nq, nt) bytes.                                   */
+int sdp_cloud_nn_workspace_size(int64_t nq, int64_t nt, size_t* bytes);
+int sdp_cloud_nn(const double* q, int64_t nq, int qstride, const double* t, int64_t nt, int tstride, double max_dist,
+                 double cell, const double* center /* or NULL */, double* nn_d2, int32_t* nn_idx, int64_t* info /* [8] */,
+                 void* workspace, size_t workspace_bytes, void* stream);
+/* Measurement hook (tools/cloud_nn_bench.py): events = HOST array of 3 hipEvent_t that every later sdp_cloud_nn
+ * of this thread records on its stream -- before the first kernel, after the grid build, after the queries;
+ * NULL switches it off.                                                                                     */
+int sdp_cloud_nn_stage_events(void* const* events);
+/* sdp_cloud_nn_stats: the sums of one direction.  nn_d2 [n] from sdp_cloud_nn, q [n][qstride] its queries
+ * (DEVICE), thresholds = HOST array of nthr <= 8 doubles in [0, max_dist] (beyond max_dist nothing was searched:
+ * such a threshold fails).  out (DEVICE) float64 [5 + nthr] = {n_finite (queries with finite coordinates),
+ * n_matched (nn_d2 < inf), sum_d = sum sqrt(d2), sum_d2, max_d (0 when nothing matched), cnt_k = #{d2 <=
+ * tau_k*tau_k (rounded product)}} over the matched.  float64 throughout, correctly rounded sqrt, partial sums of
+ * 256 points in a fixed tree and then one workgroup over the partials in a fixed order: bit-identical from run
+ * to run, no atomics.   workspace: 16-byte aligned, sdp_cloud_nn_stats_workspace_size(n) bytes.              */
+int sdp_cloud_nn_stats_workspace_size(int64_t n, size_t* bytes);
+int sdp_cloud_nn_stats(const double* nn_d2, const double* q, int qstride, int64_t n, const double* thresholds, int nthr,
+                       double max_dist, double* out, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

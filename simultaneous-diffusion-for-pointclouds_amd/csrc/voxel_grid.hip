@@ -30,6 +30,7 @@
 
 #include "../../include/sdp.h"
 #include "common.h"
+#include "voxel_grid.h"
 
 int sdp_fail(const std::string& m);
 
@@ -47,43 +48,7 @@ constexpr int VOXEL_KEY_PASSES = 5;         // keys below 2^40
 constexpr int VOXEL_LABEL_PASSES = 8;       // (voxel row, label) keys of 64 bits
 constexpr int VOXEL_SLOTS = VOXEL_SORT_ROUNDS * (VOXEL_SORT_THREADS / 64);
 constexpr int VOXEL_MAX_N = 1 << 30;
-
-struct VoxHdr {
-  float org[3];
-  float pad;
-  unsigned long long nx, ny;    // key = ix + nx*iy + nx*ny*iz
-  long long dims[3];            // nx, ny, nz as reported (each clamped to 2^62 when the grid is too large)
-  int key_bits, too_large, used, m;
-  int src[2][VOXEL_LABEL_PASSES + 1];   // [voxel keys | label keys]: the buffer pass p reads
-  int active[2][VOXEL_LABEL_PASSES];
-};
-
-struct VoxArgs {
-  const float* points;
-  const float* features;
-  const int32_t* classes;
-  int n, stride, fdim, ldim, nchunks, ntiles;
-  float dl;
-  float* out_points;
-  float* out_features;
-  int32_t* out_classes;
-  int64_t* out_keys;
-  int32_t* out_counts;
-  int32_t* out_order;
-  int32_t* out_inverse;
-  int64_t* info;
-  VoxHdr* hdr;
-  int32_t* chunk_fin;    // [nchunks] finite points per chunk, after the scan the chunks' first rows
-  float* chunk_mm;       // [nchunks][6] min xyz, max xyz of the finite points
-  int32_t* chunk_head;   // [nchunks] segment heads per chunk of sorted rows, then their first voxel rows
-  int32_t* tile_cnt;     // [256][ntiles] digit-major counts, after the scan the first output rows
-  uint64_t* key0;
-  uint64_t* key1;
-  uint32_t* idx0;
-  uint32_t* idx1;
-  int32_t* first;        // [m] first sorted row of each voxel
-  int32_t* rowof;        // [used] voxel row of each sorted row
-};
+static_assert(VOXEL_LABEL_PASSES == VOX_HDR_PASSES, "VoxHdr holds the sort state of the longer sort");
 
 SDP_DEV bool vox_finite(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
 
@@ -209,6 +174,10 @@ __global__ __launch_bounds__(VOXEL_SCAN_THREADS) void vox_grid_kernel(VoxArgs a)
     }
   }
   h->used = used;
+  for (int k = 0; k < 3; ++k) {
+    h->lo[k] = v[k];
+    h->hi[k] = v[k + 3];
+  }
   h->m = 0;
   h->too_large = 0;
   h->key_bits = 0;
@@ -549,6 +518,51 @@ static VoxLayout vox_layout(int64_t n) {
   return l;
 }
 
+static void vox_mark(int i, hipStream_t st) {
+  if (vox_events_on) (void)hipEventRecord(reinterpret_cast<hipEvent_t>(vox_events[i]), st);
+}
+
+static void vox_sort(const VoxArgs& a, int passes, int mode, hipStream_t st) {
+  const dim3 tiles(a.ntiles), one(1);
+  for (int p = 0; p < passes; ++p) {
+    hipLaunchKernelGGL(vox_hist_kernel, tiles, dim3(VOXEL_SORT_THREADS), 0, st, a, p, mode);
+    hipLaunchKernelGGL(vox_scan_digits_kernel, one, dim3(VOXEL_SCAN_THREADS), 0, st, a, p, mode);
+    hipLaunchKernelGGL(vox_scatter_kernel, tiles, dim3(VOXEL_SORT_THREADS), 0, st, a, p, mode);
+  }
+}
+
+size_t vox_workspace_bytes(int64_t n) { return vox_layout(n).total; }
+
+void vox_build_cells(VoxArgs& a, void* workspace, hipStream_t st) {
+  const VoxLayout l = vox_layout(a.n);
+  char* w = reinterpret_cast<char*>(workspace);
+  a.nchunks = l.nchunks;
+  a.ntiles = l.ntiles;
+  a.hdr = reinterpret_cast<VoxHdr*>(w + l.hdr);
+  a.chunk_fin = reinterpret_cast<int32_t*>(w + l.chunk_fin);
+  a.chunk_mm = reinterpret_cast<float*>(w + l.chunk_mm);
+  a.chunk_head = reinterpret_cast<int32_t*>(w + l.chunk_head);
+  a.tile_cnt = reinterpret_cast<int32_t*>(w + l.tile_cnt);
+  a.key0 = reinterpret_cast<uint64_t*>(w + l.key0);
+  a.key1 = reinterpret_cast<uint64_t*>(w + l.key1);
+  a.idx0 = reinterpret_cast<uint32_t*>(w + l.idx0);
+  a.idx1 = reinterpret_cast<uint32_t*>(w + l.idx1);
+  a.first = reinterpret_cast<int32_t*>(w + l.first);
+  a.rowof = reinterpret_cast<int32_t*>(w + l.rowof);
+  const dim3 chunks(l.nchunks), one(1);
+  vox_mark(0, st);
+  hipLaunchKernelGGL(vox_finite_kernel, chunks, dim3(VOXEL_CHUNK), 0, st, a);
+  hipLaunchKernelGGL(vox_grid_kernel, one, dim3(VOXEL_SCAN_THREADS), 0, st, a);
+  vox_mark(1, st);
+  hipLaunchKernelGGL(vox_keys_kernel, chunks, dim3(VOXEL_CHUNK), 0, st, a);
+  vox_mark(2, st);
+  vox_sort(a, VOXEL_KEY_PASSES, 0, st);
+  vox_mark(3, st);
+  hipLaunchKernelGGL(vox_head_count_kernel, chunks, dim3(VOXEL_CHUNK), 0, st, a);
+  hipLaunchKernelGGL(vox_scan_heads_kernel, one, dim3(VOXEL_SCAN_THREADS), 0, st, a);
+  hipLaunchKernelGGL(vox_head_scatter_kernel, chunks, dim3(VOXEL_CHUNK), 0, st, a);
+}
+
 }  // namespace sdp
 
 extern "C" {
@@ -582,10 +596,8 @@ int sdp_voxel_grid(const float* points, int64_t n, int stride, const float* feat
   if (!points || !out_points || !info || !workspace) return sdp_fail("sdp_voxel_grid: null argument");
   if (features && (fdim < 1 || fdim > 4096 || !out_features)) return sdp_fail("sdp_voxel_grid: features need 1 <= fdim <= 4096 and out_features");
   if (classes && (ldim < 1 || ldim > 4096 || !out_classes)) return sdp_fail("sdp_voxel_grid: classes need 1 <= ldim <= 4096 and out_classes");
-  const VoxLayout l = vox_layout(n);
-  if (workspace_bytes < l.total) return sdp_fail("sdp_voxel_grid: workspace too small");
+  if (workspace_bytes < vox_workspace_bytes(n)) return sdp_fail("sdp_voxel_grid: workspace too small");
   if (reinterpret_cast<uintptr_t>(workspace) % 16) return sdp_fail("sdp_voxel_grid: workspace must be 16-byte aligned");
-  char* w = reinterpret_cast<char*>(workspace);
   VoxArgs a{};
   a.points = points;
   a.features = features;
@@ -594,8 +606,6 @@ int sdp_voxel_grid(const float* points, int64_t n, int stride, const float* feat
   a.stride = stride;
   a.fdim = features ? fdim : 0;
   a.ldim = classes ? ldim : 0;
-  a.nchunks = l.nchunks;
-  a.ntiles = l.ntiles;
   a.dl = sample_dl;
   a.out_points = out_points;
   a.out_features = out_features;
@@ -605,40 +615,11 @@ int sdp_voxel_grid(const float* points, int64_t n, int stride, const float* feat
   a.out_order = out_order;
   a.out_inverse = out_inverse;
   a.info = info;
-  a.hdr = reinterpret_cast<VoxHdr*>(w + l.hdr);
-  a.chunk_fin = reinterpret_cast<int32_t*>(w + l.chunk_fin);
-  a.chunk_mm = reinterpret_cast<float*>(w + l.chunk_mm);
-  a.chunk_head = reinterpret_cast<int32_t*>(w + l.chunk_head);
-  a.tile_cnt = reinterpret_cast<int32_t*>(w + l.tile_cnt);
-  a.key0 = reinterpret_cast<uint64_t*>(w + l.key0);
-  a.key1 = reinterpret_cast<uint64_t*>(w + l.key1);
-  a.idx0 = reinterpret_cast<uint32_t*>(w + l.idx0);
-  a.idx1 = reinterpret_cast<uint32_t*>(w + l.idx1);
-  a.first = reinterpret_cast<int32_t*>(w + l.first);
-  a.rowof = reinterpret_cast<int32_t*>(w + l.rowof);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const dim3 chunks(l.nchunks), tiles(l.ntiles), one(1);
-  auto sort = [&](int passes, int mode) {
-    for (int p = 0; p < passes; ++p) {
-      hipLaunchKernelGGL(vox_hist_kernel, tiles, dim3(VOXEL_SORT_THREADS), 0, st, a, p, mode);
-      hipLaunchKernelGGL(vox_scan_digits_kernel, one, dim3(VOXEL_SCAN_THREADS), 0, st, a, p, mode);
-      hipLaunchKernelGGL(vox_scatter_kernel, tiles, dim3(VOXEL_SORT_THREADS), 0, st, a, p, mode);
-    }
-  };
-  auto mark = [&](int i) {
-    if (vox_events_on) (void)hipEventRecord(reinterpret_cast<hipEvent_t>(vox_events[i]), st);
-  };
-  mark(0);
-  hipLaunchKernelGGL(vox_finite_kernel, chunks, dim3(VOXEL_CHUNK), 0, st, a);
-  hipLaunchKernelGGL(vox_grid_kernel, one, dim3(VOXEL_SCAN_THREADS), 0, st, a);
-  mark(1);
-  hipLaunchKernelGGL(vox_keys_kernel, chunks, dim3(VOXEL_CHUNK), 0, st, a);
-  mark(2);
-  sort(VOXEL_KEY_PASSES, 0);
-  mark(3);
-  hipLaunchKernelGGL(vox_head_count_kernel, chunks, dim3(VOXEL_CHUNK), 0, st, a);
-  hipLaunchKernelGGL(vox_scan_heads_kernel, one, dim3(VOXEL_SCAN_THREADS), 0, st, a);
-  hipLaunchKernelGGL(vox_head_scatter_kernel, chunks, dim3(VOXEL_CHUNK), 0, st, a);
+  vox_build_cells(a, workspace, st);
+  const dim3 chunks(a.nchunks), one(1);
+  auto sort = [&](int passes, int mode) { vox_sort(a, passes, mode, st); };
+  auto mark = [&](int i) { vox_mark(i, st); };
   mark(4);
   const long long work = (long long)n * (3 + a.fdim);
   const int rblocks = (int)((work + 255) / 256 < 262144 ? (work + 255) / 256 : 262144);
@@ -647,7 +628,7 @@ int sdp_voxel_grid(const float* points, int64_t n, int stride, const float* feat
   for (int c = 0; c < a.ldim; ++c) {
     hipLaunchKernelGGL(vox_label_keys_kernel, chunks, dim3(VOXEL_CHUNK), 0, st, a, c);
     sort(VOXEL_LABEL_PASSES, 1);
-    hipLaunchKernelGGL(vox_vote_kernel, dim3(l.nchunks < 262144 ? l.nchunks : 262144), dim3(256), 0, st, a, c);
+    hipLaunchKernelGGL(vox_vote_kernel, dim3(a.nchunks < 262144 ? a.nchunks : 262144), dim3(256), 0, st, a, c);
   }
   hipLaunchKernelGGL(vox_info_kernel, one, one, 0, st, a);
   mark(6);

@@ -14,7 +14,10 @@ weights), --precision {fp32x3,fp32,bf16}, --num_batches (sampling batches; train
 epoch), --n_iters / --snapshot_freq / --max_epochs (override the config's training schedule),
 --save_clouds (sampling: also write each sampled doThis as a fused point cloud, {doThis}_{saveNum}_Cloud_{ckpt}.npy
 and ..._CloudOffsets_{ckpt}.npy; without it the written files are unchanged),
---cloud_grid DL (with --save_clouds: also write that cloud on a voxel grid of DL metres, ..._CloudGrid_{ckpt}.npy).
+--cloud_grid DL (with --save_clouds: also write that cloud on a voxel grid of DL metres, ..._CloudGrid_{ckpt}.npy),
+--cloud_metrics R [--cloud_metrics_cell C] (with --save_clouds: also fuse the run's reference images into a cloud and
+score the sampled cloud against it on the GPU within R metres: ..._CloudRef_, _CloudRefOffsets_, _CloudDist_ and
+_CloudMetrics_{ckpt}.npy).
 """
 import argparse
 import logging
@@ -74,7 +77,23 @@ def parse_args_and_config(argv=None):
                    help="with --save_clouds: also voxel-grid subsample each fused cloud on the GPU "
                         "(sdp.pointcloud.voxel_grid_subsample) with voxels of DL metres: "
                         "{doThis}_{saveNum}_CloudGrid_{ckpt}.npy float64 [m,4], barycentre and mean intensity")
+    p.add_argument("--cloud_metrics", type=float, default=None, metavar="R",
+                   help="with --save_clouds: also fuse the reference images the run saves (GT_completion; the masked "
+                        "input for scene completion) into a cloud with the same views, poses and masks, and score "
+                        "the sampled cloud against it on the GPU (sdp.pointcloud.nearest_neighbours) within R "
+                        "metres: {doThis}_{saveNum}_CloudRef_{ckpt}.npy, ..._CloudRefOffsets_, ..._CloudDist_ "
+                        "(distance of every sampled point to the reference, inf beyond R) and ..._CloudMetrics_ "
+                        "float64 [3, 8] (sums of both directions at thresholds (0.1, 0.2, 0.5) * min(1, R / 0.5))")
+    p.add_argument("--cloud_metrics_cell", type=float, default=None, metavar="C",
+                   help="with --cloud_metrics: cell size of the search grid, R / 8 <= C <= R (default R)")
     args = p.parse_args(argv)
+    if args.cloud_metrics is not None and not args.save_clouds:
+        p.error("--cloud_metrics needs --save_clouds")
+    if args.cloud_metrics is not None and not args.cloud_metrics > 0:
+        p.error("--cloud_metrics must be > 0")
+    if args.cloud_metrics_cell is not None and (args.cloud_metrics is None or
+                                                not 0 < args.cloud_metrics_cell <= args.cloud_metrics):
+        p.error("--cloud_metrics_cell needs --cloud_metrics R and 0 < C <= R")
     args.log_path = os.path.join(args.exp, "logs", args.doc)
     path = args.config if os.path.exists(args.config) else os.path.join("configs", args.config)
     if not os.path.exists(path):

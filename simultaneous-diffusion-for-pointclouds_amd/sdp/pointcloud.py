@@ -21,8 +21,14 @@ Two vertical origins exist in the reference and they are NOT interchangeable:
 (``sdp_voxel_grid``, csrc/voxel_grid.hip): the barycentre, the mean features and the majority labels
 of every occupied voxel, bit for bit what ``sdp.grid_subsampling.compute`` gives on the host, in
 ascending voxel key.
+
+``nearest_neighbours`` / ``cloud_metrics`` score one such cloud against another on the device
+(``sdp_cloud_nn`` / ``sdp_cloud_nn_stats``, csrc/cloud_nn.hip): the exact nearest target within a radius
+for every point, and from it Chamfer distance, accuracy / completeness and precision / recall / F-score.
 """
 from __future__ import annotations
+
+import warnings
 
 import numpy as np
 import torch
@@ -156,6 +162,174 @@ def voxel_grid_subsample(points, features=None, classes=None, sampleDl=0.1, cent
     if return_inverse:
         out.append(inverse)
     return out[0] if len(out) == 1 else tuple(out)
+
+
+def _xyz64(t, what):
+    if not torch.is_tensor(t) or not t.is_cuda or t.dim() != 2 or t.shape[1] not in (3, 4):
+        raise ValueError(f"{what} must be a cuda [n,3] or [n,4] tensor of points")
+    if t.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"{what} must be float32 or float64")
+    return t.to(torch.float64).contiguous()
+
+
+def _nn_launch(q, t, max_dist, cell, center):
+    """sdp_cloud_nn on prepared float64 tensors; no host sync.  Returns (d2, index, info [9]): the entry's
+    info [8] and, last, whether the centre is finite (a non-finite one would empty the grid silently)."""
+    dev = q.device
+    if center is None:
+        # the midpoint of the target's finite bounds (zeros when it has no finite point), on the device
+        xyz = t[:, :3]
+        fin = torch.isfinite(xyz).all(1, keepdim=True)
+        inf = torch.full((1, 3), float("inf"), dtype=torch.float64, device=dev)
+        lo = torch.cat((torch.where(fin, xyz, inf), inf)).amin(0)
+        hi = torch.cat((torch.where(fin, xyz, -inf), -inf)).amax(0)
+        c64 = torch.nan_to_num(lo * 0.5 + hi * 0.5, nan=0.0, posinf=0.0, neginf=0.0)
+    else:
+        c64 = torch.as_tensor(center, dtype=torch.float64).to(dev).reshape(3).contiguous()
+    L = _lib.lib()
+    nq, nt = q.shape[0], t.shape[0]
+    nb = _lib.SZ()
+    _lib.check(L.sdp_cloud_nn_workspace_size(nq, nt, _lib.C.byref(nb)), "cloud_nn_ws")
+    with torch.cuda.device(dev):
+        ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+        d2 = torch.empty(nq, dtype=torch.float64, device=dev)
+        idx = torch.empty(nq, dtype=torch.int32, device=dev)
+        info = torch.empty(8, dtype=torch.int64, device=dev)
+        _lib.check(L.sdp_cloud_nn(_lib.ptr(q) if nq else None, nq, q.shape[1], _lib.ptr(t) if nt else None, nt,
+                                  t.shape[1], float(max_dist), float(cell), c64.data_ptr(), _lib.ptr(d2) if nq else None,
+                                  _lib.ptr(idx) if nq else None, info.data_ptr(), ws.data_ptr(), ws.numel(),
+                                  _lib.stream()), "cloud_nn")
+    return d2, idx, torch.cat((info, torch.isfinite(c64).all().to(torch.int64).reshape(1)))
+
+
+def _nn_check(info, max_dist, cell, what):
+    """Raise / warn from the host copy of ``_nn_launch``'s info."""
+    st, nx, ny, nz = (int(v) for v in info[:4])
+    if not int(info[8]):
+        raise ValueError(f"{what}: center must be finite")
+    if int(info[6]):
+        warnings.warn(f"{what}: the float32 grid origin rounded above the targets' lower bound at cell = {cell}; "
+                      "every query scanned all targets (exact, but slow): change cell or center slightly",
+                      RuntimeWarning, stacklevel=3)
+    if st == -1:
+        raise RuntimeError(f"{what}: a grid of {nx} x {ny} x {nz} cells at cell = {cell} exceeds 2^40 cells")
+    if st == -2:
+        raise RuntimeError(f"{what}: cell = {cell} too small for max_dist = {max_dist} on a float32 grid of "
+                           f"{nx} x {ny} x {nz} cells ({int(info[5])} rings needed, 9 allowed): use a larger "
+                           "cell or a center near the cloud")
+
+
+def _nn_args(max_dist, cell, what):
+    if not max_dist > 0 or not np.isfinite(max_dist):
+        raise ValueError(f"{what}: max_dist must be > 0 and finite")
+    cell = max_dist if cell is None else cell
+    if not 0 < cell <= max_dist:
+        raise ValueError(f"{what}: cell must be in (0, max_dist]")
+    return float(max_dist), float(cell)
+
+
+def nearest_neighbours(query, target, max_dist, cell=None, center=None):
+    """For every point of ``query`` the exact nearest point of ``target`` within ``max_dist``, on the device.
+
+    query, target: cuda [n,3] or [n,4] (xyz first), float64 (float32 is widened).  Returns (d2 float64 [nq],
+    index int32 [nq]): d2 = ((dx*dx + dy*dy) + dz*dz) in float64 from the given coordinates, the target of
+    smallest d2 <= max_dist*max_dist, among equals the smallest index; +inf and -1 for a query without one or
+    with a non-finite coordinate.  A target with a non-finite coordinate is never a neighbour.  ``cell``
+    (default max_dist, at least max_dist / 8) and ``center`` (float64 [3], default the midpoint of the target's
+    finite bounds) only steer the float32 acceleration grid; the result does not depend on them.  One host
+    sync, to read the grid's status.  Raises RuntimeError when the grid exceeds 2^40 cells or the cell is too
+    small for max_dist."""
+    what = "nearest_neighbours"
+    q, t = _xyz64(query, "query"), _xyz64(target, "target")
+    if q.device != t.device:
+        raise ValueError("query and target must be on the same device")
+    max_dist, cell = _nn_args(max_dist, cell, what)
+    d2, idx, info = _nn_launch(q, t, max_dist, cell, center)
+    _nn_check(info.tolist(), max_dist, cell, what)
+    return d2, idx
+
+
+def _nn_stats_launch(d2, q, thresholds, max_dist):
+    L = _lib.lib()
+    n, T = q.shape[0], len(thresholds)
+    nb = _lib.SZ()
+    _lib.check(L.sdp_cloud_nn_stats_workspace_size(n, _lib.C.byref(nb)), "cloud_nn_stats_ws")
+    with torch.cuda.device(q.device):
+        ws = torch.empty(nb.value, dtype=torch.uint8, device=q.device)
+        out = torch.empty(5 + T, dtype=torch.float64, device=q.device)
+        thr = (_lib.D * max(T, 1))(*thresholds)
+        _lib.check(L.sdp_cloud_nn_stats(_lib.ptr(d2) if n else None, _lib.ptr(q) if n else None, q.shape[1], n, thr, T,
+                                        float(max_dist), out.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream()),
+                   "cloud_nn_stats")
+    return out
+
+
+def nearest_neighbour_stats(d2, query, thresholds, max_dist):
+    """The sums of one direction (``sdp_cloud_nn_stats``): cuda float64 [5 + T] = n_finite, n_matched,
+    sum of distances, sum of squared distances, largest distance, then per threshold tau the number of points
+    with d2 <= tau*tau.  ``d2`` from ``nearest_neighbours(query, ...)``; thresholds above max_dist raise."""
+    q = _xyz64(query, "query")
+    if not d2.is_cuda or d2.dtype != torch.float64 or tuple(d2.shape) != (q.shape[0],):
+        raise ValueError("d2 must be the cuda float64 [n] result of nearest_neighbours on this query")
+    return _nn_stats_launch(d2.contiguous(), q, [float(v) for v in thresholds], max_dist)
+
+
+def cloud_distance_stats(a, b, max_dist, thresholds=(0.1, 0.2, 0.5), cell=None):
+    """Both directions between clouds ``a`` and ``b`` on the device: (d2 float64 [n_a], the squared distance of
+    every point of ``a`` to its nearest point of ``b`` within max_dist, +inf without one; rows float64
+    [2, 5 + T], the sums of ``nearest_neighbour_stats`` for a -> b and b -> a).  One host sync, to read the
+    grids' status: raises like ``nearest_neighbours``."""
+    what = "cloud_distance_stats"
+    a64, b64 = _xyz64(a, "a"), _xyz64(b, "b")
+    if a64.device != b64.device:
+        raise ValueError("a and b must be on the same device")
+    max_dist, cell = _nn_args(max_dist, cell, what)
+    thr = [float(v) for v in thresholds]
+    if len(thr) > 8 or any(not 0 <= v <= max_dist for v in thr):
+        raise ValueError(f"{what}: at most 8 thresholds, each in [0, max_dist]")
+    rows, infos, fwd = [], [], None
+    for q, t in ((a64, b64), (b64, a64)):
+        d2, _, info = _nn_launch(q, t, max_dist, cell, None)
+        rows.append(_nn_stats_launch(d2, q, thr, max_dist))
+        infos.append(info)
+        fwd = d2 if fwd is None else fwd
+    for info in torch.stack(infos).tolist():
+        _nn_check(info, max_dist, cell, what)
+    return fwd, torch.stack(rows)
+
+
+def metrics_from_stats(ab, ba, thresholds):
+    """The dict of ``cloud_metrics`` from the two [5 + T] stat rows (host numbers)."""
+    out = {}
+    for name, r in (("ab", ab), ("ba", ba)):
+        n, matched = float(r[0]), float(r[1])
+        out[name] = {"n": int(n), "matched": int(matched),
+                     "mean": float(r[2]) / matched if matched else float("nan"),
+                     "rms": float(np.sqrt(float(r[3]) / matched)) if matched else float("nan"),
+                     "max": float(r[4]), "within": [int(v) for v in r[5:]]}
+    out["chamfer"] = out["ab"]["mean"] + out["ba"]["mean"]
+    out["thresholds"] = [float(v) for v in thresholds]
+    pr = [w / out["ab"]["n"] if out["ab"]["n"] else 0.0 for w in out["ab"]["within"]]
+    rc = [w / out["ba"]["n"] if out["ba"]["n"] else 0.0 for w in out["ba"]["within"]]
+    out["precision"], out["recall"] = pr, rc
+    out["fscore"] = [2 * p * r / (p + r) if p + r > 0 else 0.0 for p, r in zip(pr, rc)]
+    return out
+
+
+def cloud_metrics(a, b, max_dist, thresholds=(0.1, 0.2, 0.5), cell=None):
+    """Chamfer distance and precision / recall / F-score between clouds ``a`` (e.g. a completion) and ``b``
+    (e.g. its reference), from the exact nearest neighbours within ``max_dist`` in both directions.
+
+    Returns {"ab": {n, matched, mean, rms, max, within[k]}, "ba": {...}, "chamfer": mean_ab + mean_ba,
+    "thresholds", "precision"[k] = within_ab[k] / n_a, "recall"[k] = within_ba[k] / n_b, "fscore"[k] =
+    2PR / (P + R) or 0}.  n counts the points with finite coordinates, matched those with a neighbour within
+    max_dist; mean / rms / max run over the matched (NaN when none), so a point farther than max_dist from
+    the other cloud lowers precision / recall but not the means.  Thresholds must not exceed max_dist.
+    Everything runs on the device (``cloud_distance_stats``); the host reads the grids' status and the two rows of sums at the end."""
+    thr = [float(v) for v in thresholds]
+    _, rows = cloud_distance_stats(a, b, max_dist, thr, cell)
+    ab, ba = rows.tolist()
+    return metrics_from_stats(ab, ba, thr)
 
 
 def fuse_views(x, origins=None, poses=None, keep=None, exist=None, min_range=1.5, geometry="dataset",

@@ -15,7 +15,9 @@ Images are saved as inverse_data_transform (clamp [0,1], datasets/__init__.py:20
 transposed to [2B',3,H,W] (rows [0,B') depth, [B',2B') intensity, 3 identical channels).
 With ``args.save_clouds`` every sampled doThis also writes its views as one fused point cloud
 (``_save_clouds``): {doThis}_{saveNum}_Cloud_{ckpt}.npy and {doThis}_{saveNum}_CloudOffsets_{ckpt}.npy;
-with ``args.cloud_grid`` = DL besides them {doThis}_{saveNum}_CloudGrid_{ckpt}.npy, that cloud on a voxel grid of DL metres.
+with ``args.cloud_grid`` = DL besides them {doThis}_{saveNum}_CloudGrid_{ckpt}.npy, that cloud on a voxel grid of DL metres;
+with ``args.cloud_metrics`` = R the reference images of the same views as a cloud and the distances between the two
+(``_CloudRef_``, ``_CloudRefOffsets_``, ``_CloudDist_``, ``_CloudMetrics_``).
 
 Data: with ``args.kitti_root`` the views come from the KITTI-360 datasets of sdp.kitti360
 (rendered on the GPU) in the order of the reference's MySampler over the pose file
@@ -180,7 +182,7 @@ class Runner:
         torch.distributed.all_gather_object(objs, None if t is None else t.numpy())
         return torch.from_numpy(np.concatenate([o for o in objs if o is not None]))
 
-    def _save_clouds(self, stem, ck, sample, notsky, origins=None, poses=None):
+    def _save_clouds(self, stem, ck, sample, notsky, origins=None, poses=None, reference=None):
         """--save_clouds: the sampled views of one doThis as a fused cloud, the offline step of
         MeasureResults/SceneCompleter.py:43-121, 259-264 on the GPU (sdp.pointcloud).  ``sample`` is the
         clamped inverse_data_transform image [n,C,H,W] that Masked_completion holds, unprojected with
@@ -191,15 +193,24 @@ class Runner:
         With --cloud_grid DL also {stem}_CloudGrid_{ck}.npy, float64 [m,4]: the barycentre and the mean
         intensity of every occupied DL-metre voxel of that cloud (sdp.pointcloud.voxel_grid_subsample), in
         ascending voxel key, the float32 grid centred on the translation of the first view's pose or
-        origin (zeros without either)."""
+        origin (zeros without either).
+        With --cloud_metrics R, ``reference`` [n,C,H,W] -- the images the run saves as its reference, for these
+        views -- is fused the same way (same poses / origins, masks and minimum range) and the two clouds are
+        scored against each other on the device (sdp.pointcloud.nearest_neighbours within R, cell
+        --cloud_metrics_cell): {stem}_CloudRef_{ck}.npy float64 [rows,4], {stem}_CloudRefOffsets_{ck}.npy,
+        {stem}_CloudDist_{ck}.npy float64 [rows of _Cloud_] = the distance of every sampled point to its nearest
+        reference point, +inf beyond R, and {stem}_CloudMetrics_{ck}.npy float64 [3, 5+T], T = 3: row 0 sampled ->
+        reference, row 1 reference -> sampled, each [n_finite, n_matched, sum_d, sum_d2, max_d, cnt_0..] at the
+        thresholds tau = (0.1, 0.2, 0.5) * min(1, R / 0.5); row 2 [R, cell, T, 0, 0, tau_0..]."""
         from .pointcloud import range_image_to_point_cloud, voxel_grid_subsample
         n, _, H, W = sample.shape
         d = self.device
         f64 = lambda t: None if t is None else t.to(d, torch.float64).contiguous()
-        pts, off = range_image_to_point_cloud(
-            sample.to(d, torch.float32), origins=f64(origins), poses=f64(poses),
+        fuse = lambda img: range_image_to_point_cloud(
+            img.to(d, torch.float32), origins=f64(origins), poses=f64(poses),
             keep=notsky.reshape(n, H, W).to(d), exist=torch.from_numpy(synthetic.exist_mask(H, W)).to(d),
             min_range=1.5, geometry="dataset")
+        pts, off = fuse(sample)
         np.save(os.path.join(self.args.image_folder, f"{stem}_Cloud_{ck}.npy"), pts.cpu().numpy())
         np.save(os.path.join(self.args.image_folder, f"{stem}_CloudOffsets_{ck}.npy"), off.cpu().numpy())
         dl = getattr(self.args, "cloud_grid", None)
@@ -215,6 +226,19 @@ class Runner:
             else:
                 grid = pts
             np.save(os.path.join(self.args.image_folder, f"{stem}_CloudGrid_{ck}.npy"), grid.cpu().numpy())
+        R = getattr(self.args, "cloud_metrics", None)
+        if R:
+            from .pointcloud import cloud_distance_stats
+            cell = float(getattr(self.args, "cloud_metrics_cell", None) or R)
+            thr = [t * min(1.0, R / 0.5) for t in (0.1, 0.2, 0.5)]
+            rpts, roff = fuse(reference)
+            fwd, rows = cloud_distance_stats(pts, rpts, float(R), thr, cell)
+            last = torch.tensor([R, cell, len(thr), 0.0, 0.0] + thr, dtype=torch.float64, device=d)
+            out = lambda kind, t: np.save(os.path.join(self.args.image_folder, f"{stem}_{kind}_{ck}.npy"), t.cpu().numpy())
+            out("CloudRef", rpts)
+            out("CloudRefOffsets", roff)
+            out("CloudDist", torch.from_numpy(np.sqrt(fwd.cpu().numpy())))   # correctly rounded; inf stays inf
+            out("CloudMetrics", torch.cat((rows, last.reshape(1, -1))))
 
     def _cloud_poses(self, toWorld, k, kitti):
         """Sensor -> world matrix of every sampled view ([n,4,4] float64; k = views kept per megabatch), so
@@ -342,7 +366,15 @@ class Runner:
                     np.save(os.path.join(folder, f"{do}_{save_num}_Shared_completion_initial{ck}.pth"),
                             to_grid_layout(shared).numpy())
                 if getattr(self.args, "save_clouds", False):
-                    self._save_clouds(f"{do}_{save_num}", ck, sample, sky, poses=self._cloud_poses(toWorld, k, kitti))
+                    reference = None
+                    if getattr(self.args, "cloud_metrics", None):
+                        # what GT_completion holds, for the views sampled here: the goal scans (kitti), else the
+                        # masked input -- the reference's quirk, kept
+                        gt_full = goal if kitti else ref_full * mask_full
+                        reference = inverse_data_transform(
+                            gt_full if k == aB else _first_views(gt_full, n_mega, aB, k)).float()
+                    self._save_clouds(f"{do}_{save_num}", ck, sample, sky, poses=self._cloud_poses(toWorld, k, kitti),
+                                      reference=reference)
 
     # ------------------------------------------------------------------------------ scene completion
     def _completion_source(self, B, aB, H, W):
@@ -441,7 +473,9 @@ class Runner:
                 np.save(os.path.join(folder, f"{do}_{bi}_Shared_completion_initial{ck}.pth"), initial.numpy())
                 if getattr(self.args, "save_clouds", False):
                     self._save_clouds(f"{do}_{save_num}", ck,
-                                      inverse_data_transform(final.view(B, c.data.channels, H, W)), sky_full, origins=mods)
+                                      inverse_data_transform(final.view(B, c.data.channels, H, W)), sky_full, origins=mods,
+                                      reference=inverse_data_transform(ref_full * mask_full).float()
+                                      if getattr(self.args, "cloud_metrics", None) else None)
 
     # ------------------------------------------------------------------------------ training
     def _train_source(self, Bt, rank, world):
