@@ -147,6 +147,20 @@ size_t sdpk_head_wgrad_part_floats(int B, int H, int W);
  * reference clears it.  3 <= H, 1 <= W <= 1024 */
 int sdpk_range_sky_scan(const double* xy, int H, int W, uint8_t* obf, uint8_t* sky, void* stream);
 
+/* ---- the shared primitives of the point-cloud back end (csrc/device_prims.h, csrc/radix_sort.hip) */
+/* one workgroup: exclusive scan of data[0..n) in place, the sum to *total; 4096 counts per iteration.  n >= 0 */
+int sdpk_block_scan(int32_t* data, int n, int32_t* total, void* stream);
+/* Stable LSD radix sort, 8-bit digits 0 .. passes-1, tiles of 1024 elements, of the keys in key0 (with the values
+ * in val0; val0 = val1 = null: keys only) between the ping/pong buffers of `capacity` elements each.
+ * tile_cnt: 256 * ceil(capacity / 1024) int32 of scratch.  params: DEVICE int32 [3] = the element count
+ * (0 <= n <= capacity, the caller's duty), the key width in bits (a pass at or beyond it moves nothing) and a
+ * flag, non-zero = do nothing.  state: DEVICE int32 [SDPK_RADIX_STATE_INTS], zeroed by the caller (csrc/radix_sort.h
+ * RadixState); afterwards state[SDPK_RADIX_STATE_RESULT] tells which buffer (0 | 1) holds the sorted elements */
+#define SDPK_RADIX_STATE_INTS 18
+#define SDPK_RADIX_STATE_RESULT 17
+int sdpk_radix_sort(uint64_t* key0, uint64_t* key1, uint32_t* val0, uint32_t* val1, int32_t* tile_cnt, int64_t capacity,
+                    const int32_t* params, int32_t* state, int passes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,7 @@
 //   nn_center_kernel    pf = float32(t - center) of every target, a coordinate beyond float32 clamped to
 //                       +-FLT_MAX (a target that is finite in float64 must not drop out of the grid)
 //   vox_build_cells     voxel_grid.hip's front on pf with cell size float32(cell): bounds, org, nx, ny, nz,
-//                       key = ix + nx*iy + nx*ny*iz, the stable radix sort of (key, target index), segment heads
+//                       key = ix + nx*iy + nx*ny*iz, the stable sort of (key, target index) (radix_sort.hip), heads
 //                       -> sorted unique keys [m], the first sorted row of every cell, the permutation
 //   nn_plan_kernel      ONE thread: slack, K, the status and info[8]
 //   nn_query_kernel     one query per lane: its own signed cell from the same float32 arithmetic, then the rings
@@ -48,13 +48,11 @@
 // metres); info[6] reports it, the Python wrappers warn, tests/test_gpu_cloud_nn.py forces it.
 #include <cfloat>
 #include <cmath>
-#include <string>
 
 #include "../../include/sdp.h"
+#include "capi.h"
 #include "common.h"
 #include "voxel_grid.h"
-
-int sdp_fail(const std::string& m);
 
 namespace sdp {
 
@@ -298,33 +296,19 @@ __global__ __launch_bounds__(NN_THREADS) void nn_stat_final_kernel(NnStatArgs a)
 }
 
 // measurement hook (sdp_cloud_nn_stage_events): start, after the grid build, after the queries
-constexpr int NN_STAGE_EVENTS = 3;
-static thread_local void* nn_events[NN_STAGE_EVENTS];
-static thread_local bool nn_events_on = false;
+static thread_local StageEvents<3> nn_events;
 
-static size_t nn_align(size_t b) { return (b + 255) / 256 * 256; }
-
-struct NnLayout {
-  size_t plan, pf, keys, order, vox, total;
-};
-
-static NnLayout nn_layout(int64_t nt) {
-  NnLayout l{};
-  size_t o = 0;
-  auto take = [&o](size_t bytes) {
-    const size_t at = o;
-    o += nn_align(bytes);
-    return at;
-  };
-  l.plan = take(sizeof(NnPlan));
+// points a.plan .. a.order and vox_ws into the workspace at `w` (0: only count); returns the bytes
+static size_t nn_place(NnArgs& a, char*& vox_ws, int64_t nt, uintptr_t w) {
+  Layout l{w};
+  l.take(a.plan, sizeof(NnPlan));
   if (nt > 0) {
-    l.pf = take((size_t)nt * 12);
-    l.keys = take((size_t)nt * 8);
-    l.order = take((size_t)nt * 4);
-    l.vox = take(vox_workspace_bytes(nt));
+    l.take(a.pf, (size_t)nt * 12);
+    l.take(a.keys, (size_t)nt * 8);
+    l.take(a.order, (size_t)nt * 4);
+    l.take(vox_ws, vox_workspace_bytes(nt));
   }
-  l.total = o;
-  return l;
+  return l.bytes;
 }
 
 }  // namespace sdp
@@ -334,21 +318,13 @@ extern "C" {
 int sdp_cloud_nn_workspace_size(int64_t nq, int64_t nt, size_t* bytes) {
   if (!bytes || nq < 0 || nt < 0 || nq > sdp::NN_MAX_N || nt > sdp::NN_MAX_N)
     return sdp_fail("sdp_cloud_nn_workspace_size: nq and nt must be in [0, 2^30]");
-  *bytes = sdp::nn_layout(nt).total;
+  sdp::NnArgs a{};
+  char* vox_ws = nullptr;
+  *bytes = sdp::nn_place(a, vox_ws, nt, 0);
   return 0;
 }
 
-int sdp_cloud_nn_stage_events(void* const* events) {
-  sdp::nn_events_on = events != nullptr;
-  for (int i = 0; i < sdp::NN_STAGE_EVENTS; ++i) sdp::nn_events[i] = events ? events[i] : nullptr;
-  if (events)
-    for (int i = 0; i < sdp::NN_STAGE_EVENTS; ++i)
-      if (!events[i]) {
-        sdp::nn_events_on = false;
-        return sdp_fail("sdp_cloud_nn_stage_events: null event");
-      }
-  return 0;
-}
+int sdp_cloud_nn_stage_events(void* const* events) { return sdp::nn_events.set(events, "sdp_cloud_nn_stage_events"); }
 
 int sdp_cloud_nn(const double* q, int64_t nq, int qstride, const double* t, int64_t nt, int tstride, double max_dist,
                  double cell, const double* center, double* nn_d2, int32_t* nn_idx, int64_t* info, void* workspace,
@@ -362,12 +338,12 @@ int sdp_cloud_nn(const double* q, int64_t nq, int qstride, const double* t, int6
     return sdp_fail("sdp_cloud_nn: cell too small for max_dist (max_dist / cell must be <= 8)");
   if ((qstride != 3 && qstride != 4) || (tstride != 3 && tstride != 4)) return sdp_fail("sdp_cloud_nn: stride must be 3 or 4");
   if (!info || !workspace || (nq > 0 && (!q || !nn_d2 || !nn_idx)) || (nt > 0 && !t)) return sdp_fail("sdp_cloud_nn: null argument");
-  const NnLayout l = nn_layout(nt);
-  if (workspace_bytes < l.total) return sdp_fail("sdp_cloud_nn: workspace too small");
-  if (reinterpret_cast<uintptr_t>(workspace) % 16) return sdp_fail("sdp_cloud_nn: workspace must be 16-byte aligned");
-  char* w = reinterpret_cast<char*>(workspace);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   NnArgs a{};
+  char* vox_ws = nullptr;
+  if (workspace_bytes < nn_place(a, vox_ws, nt, reinterpret_cast<uintptr_t>(workspace)))
+    return sdp_fail("sdp_cloud_nn: workspace too small");
+  if (reinterpret_cast<uintptr_t>(workspace) % 16) return sdp_fail("sdp_cloud_nn: workspace must be 16-byte aligned");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   a.q = q;
   a.t = t;
   a.center = center;
@@ -380,10 +356,7 @@ int sdp_cloud_nn(const double* q, int64_t nq, int qstride, const double* t, int6
   a.nn_d2 = nn_d2;
   a.nn_idx = nn_idx;
   a.info = info;
-  a.plan = reinterpret_cast<NnPlan*>(w + l.plan);
-  auto mark = [&](int i) {
-    if (nn_events_on) (void)hipEventRecord(reinterpret_cast<hipEvent_t>(nn_events[i]), st);
-  };
+  auto mark = [&](int i) { nn_events.mark(i, st); };
   const dim3 one(1), threads(NN_THREADS), qblocks((unsigned)((nq + NN_THREADS - 1) / NN_THREADS));
   mark(0);
   if (nt == 0 || nq == 0) {
@@ -392,9 +365,6 @@ int sdp_cloud_nn(const double* q, int64_t nq, int qstride, const double* t, int6
     mark(1);
     mark(2);
   } else {
-    a.pf = reinterpret_cast<float*>(w + l.pf);
-    a.keys = reinterpret_cast<int64_t*>(w + l.keys);
-    a.order = reinterpret_cast<int32_t*>(w + l.order);
     a.vox.points = a.pf;
     a.vox.n = (int)nt;
     a.vox.stride = 3;
@@ -402,19 +372,18 @@ int sdp_cloud_nn(const double* q, int64_t nq, int qstride, const double* t, int6
     a.vox.out_keys = a.keys;
     a.vox.out_order = a.order;
     hipLaunchKernelGGL(nn_center_kernel, dim3((unsigned)((nt + NN_THREADS - 1) / NN_THREADS)), threads, 0, st, a);
-    vox_build_cells(a.vox, w + l.vox, st);
+    vox_build_cells(a.vox, vox_ws, st);
     hipLaunchKernelGGL(nn_plan_kernel, one, one, 0, st, a);
     mark(1);
     hipLaunchKernelGGL(nn_query_kernel, qblocks, threads, 0, st, a);
     mark(2);
   }
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : sdp_fail(std::string("sdp_cloud_nn: ") + hipGetErrorString(e));
+  return launch_status("sdp_cloud_nn");
 }
 
 int sdp_cloud_nn_stats_workspace_size(int64_t n, size_t* bytes) {
   if (!bytes || n < 0 || n > sdp::NN_MAX_N) return sdp_fail("sdp_cloud_nn_stats_workspace_size: n must be in [0, 2^30]");
-  *bytes = sdp::nn_align((size_t)((n + sdp::NN_THREADS - 1) / sdp::NN_THREADS) * sdp::NN_STAT_COLS * 8) + 256;
+  *bytes = sdp::align256((size_t)((n + sdp::NN_THREADS - 1) / sdp::NN_THREADS) * sdp::NN_STAT_COLS * 8) + 256;
   return 0;
 }
 
@@ -447,8 +416,7 @@ int sdp_cloud_nn_stats(const double* nn_d2, const double* q, int qstride, int64_
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (a.nblocks > 0) hipLaunchKernelGGL(nn_stat_partial_kernel, dim3(a.nblocks), dim3(NN_THREADS), 0, st, a);
   hipLaunchKernelGGL(nn_stat_final_kernel, dim3(1), dim3(NN_THREADS), 0, st, a);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : sdp_fail(std::string("sdp_cloud_nn_stats: ") + hipGetErrorString(e));
+  return launch_status("sdp_cloud_nn_stats");
 }
 
 }  // extern "C"

@@ -5,9 +5,9 @@
 #include <string>
 
 #include "../../include/sdp_kernels.h"
+#include "capi.h"
 #include "kernels.h"
-
-int sdp_fail(const std::string& m);   // net.hip: sets sdp_last_error(), returns -1
+#include "radix_sort.h"
 
 using namespace sdp;
 
@@ -201,6 +201,35 @@ size_t sdpk_head_wgrad_part_floats(int B, int H, int W) { return head_wgrad_part
 
 int sdpk_range_sky_scan(const double* xy, int H, int W, uint8_t* obf, uint8_t* sky, void* stream) {
   return done(range_sky_scan(xy, H, W, obf, sky, S(stream)), "sdpk_range_sky_scan");
+}
+
+int sdpk_block_scan(int32_t* data, int n, int32_t* total, void* stream) {
+  if (!data || !total || n < 0) return sdp_fail("sdpk_block_scan: null argument or n < 0");
+  return done(block_scan(data, n, total, S(stream)), "sdpk_block_scan");
+}
+
+int sdpk_radix_sort(uint64_t* key0, uint64_t* key1, uint32_t* val0, uint32_t* val1, int32_t* tile_cnt, int64_t capacity,
+                    const int32_t* params, int32_t* state, int passes, void* stream) {
+  static_assert(sizeof(RadixState) == SDPK_RADIX_STATE_INTS * sizeof(int32_t) &&
+                    offsetof(RadixState, result) == SDPK_RADIX_STATE_RESULT * sizeof(int32_t),
+                "sdp_kernels.h describes RadixState");
+  if (!key0 || !key1 || !tile_cnt || !params || !state || (val0 == nullptr) != (val1 == nullptr))
+    return sdp_fail("sdpk_radix_sort: null argument");
+  if (capacity < 1 || capacity > (1 << 30) || passes < 0 || passes > RADIX_MAX_PASSES)
+    return sdp_fail("sdpk_radix_sort: capacity must be in [1, 2^30] and passes in [0, 8]");
+  RadixArgs a{};
+  a.key0 = key0;
+  a.key1 = key1;
+  a.val0 = val0;
+  a.val1 = val1;
+  a.tile_cnt = tile_cnt;
+  a.ntiles = (int)((capacity + RADIX_TILE - 1) / RADIX_TILE);
+  a.n = params;
+  a.bits = params + 1;
+  a.skip = params + 2;
+  a.state = reinterpret_cast<RadixState*>(state);
+  radix_sort(a, passes, S(stream));
+  return launch_status("sdpk_radix_sort");
 }
 
 }  // extern "C"

@@ -18,10 +18,9 @@
 #include <string>
 
 #include "../../include/sdp.h"
+#include "capi.h"
 #include "common.h"
 #include "kernels.h"
-
-int sdp_fail(const std::string& m);
 
 namespace sdp {
 
@@ -154,8 +153,7 @@ int sdp_view_transform(const float* points, int64_t n, const double* m1, const d
   hipLaunchKernelGGL(sdp::view_transform_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const float4*>(points), (long long)n, A,
                      B, nmat, reinterpret_cast<double4*>(out));
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : sdp_fail(std::string("sdp_view_transform: ") + hipGetErrorString(e));
+  return sdp::launch_status("sdp_view_transform");
 }
 
 int sdp_view_gather(const int64_t* index, int H, int W, int blank_cols, const float* points, double* out, int* count,
@@ -164,8 +162,7 @@ int sdp_view_gather(const int64_t* index, int H, int W, int blank_cols, const fl
     return sdp_fail("sdp_view_gather: bad argument");
   hipLaunchKernelGGL(sdp::view_gather_kernel, dim3(1), dim3(1024), 0, reinterpret_cast<hipStream_t>(stream), index, H,
                      W, blank_cols, reinterpret_cast<const float4*>(points), reinterpret_cast<double4*>(out), count);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : sdp_fail(std::string("sdp_view_gather: ") + hipGetErrorString(e));
+  return sdp::launch_status("sdp_view_gather");
 }
 
 int sdp_view_finalize(const double* depth, const double* intensity, const uint8_t* obfuscation, const uint8_t* sky,
@@ -182,8 +179,7 @@ int sdp_view_finalize(const double* depth, const double* intensity, const uint8_
                       H, W, channels, roll, variant, first_view};
   hipLaunchKernelGGL(sdp::view_finalize_kernel, dim3((H * W + 255) / 256), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), a);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : sdp_fail(std::string("sdp_view_finalize: ") + hipGetErrorString(e));
+  return sdp::launch_status("sdp_view_finalize");
 }
 
 }  // extern "C"

@@ -3,9 +3,8 @@
 #include <string>
 
 #include "../../include/sdp.h"
+#include "capi.h"
 #include "merge.h"
-
-int sdp_fail(const std::string& m);
 
 // reference evaluation order: no FMA contraction in this file (HIP __fmul_rn is a plain `*`)
 #pragma clang fp contract(off)

@@ -17,10 +17,9 @@
 #include <string>
 
 #include "../../include/sdp.h"
+#include "capi.h"
 #include "common.h"
 #include "kernels.h"
-
-int sdp_fail(const std::string& m);
 
 namespace sdp {
 

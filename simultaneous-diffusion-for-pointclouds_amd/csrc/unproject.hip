@@ -7,27 +7,25 @@
 //   unproj_count_kernel   : one workgroup per chunk of UNPROJ_CHUNK pixels of one view; its keep count,
 //                           and (spread over the workgroups) the (cos, sin) table of the W azimuths and
 //                           H elevations
-//   unproj_scan_kernel    : ONE workgroup; exclusive scan of the chunk counts in place (tiles of
-//                           UNPROJ_SCAN_THREADS * UNPROJ_SCAN_PER_THREAD chunks with a running carry)
-//                           and offsets[B+1]
-//   unproj_scatter_kernel : the predicate again, in-chunk rank = wave ballot + LDS wave prefix, one
-//                           32-byte row per kept pixel at base[chunk] + rank
+//   unproj_scan_kernel    : ONE workgroup; exclusive scan of the chunk counts in place and offsets[B+1]
+//   unproj_scatter_kernel : the predicate again and its in-chunk rank, one 32-byte row per kept pixel at
+//                           base[chunk] + rank
 // so the row order is fixed by the pixel order alone and the result is bit-identical from run to run.
+// The scan and the chunk count / rank: device_prims.h ("Shared device primitives").
 // Distance as oracle/sampling_ref.real_distance with smod = 1: v = f32(|code|*6),
 // rd = f32(2^v) - 1 in float32 with 2^v rounded once from its float64 value (numpy's float32 power,
 // which SceneCompleter calls, is not correctly rounded); everything after that is float64, no contraction.
-#include <string>
-
 #include "../../include/sdp.h"
-#include "common.h"
-
-int sdp_fail(const std::string& m);
+#include "capi.h"
+#include "device_prims.h"
 
 namespace sdp {
 
 constexpr int UNPROJ_CHUNK = 256;           // pixels per workgroup = threads per workgroup (4 waves)
-constexpr int UNPROJ_SCAN_THREADS = 1024;   // the scan kernel's one workgroup
-constexpr int UNPROJ_SCAN_PER_THREAD = 4;   // consecutive chunks per thread: 4096 chunks (16 views of 64x1024) per iteration
+constexpr int UNPROJ_SCAN_THREADS = 1024;   // the scan kernel's one workgroup ...
+constexpr int UNPROJ_SCAN_PER_THREAD = 4;   // ... and chunks per thread (the tests size their scan case by the two)
+static_assert(UNPROJ_CHUNK == CHUNK_THREADS && UNPROJ_SCAN_THREADS == SCAN_THREADS &&
+                  UNPROJ_SCAN_PER_THREAD == SCAN_PER_THREAD, "the primitives of device_prims.h");
 
 struct UnprojArgs {
   const float* x;               // [B][C][H][W]
@@ -70,58 +68,21 @@ __global__ __launch_bounds__(UNPROJ_CHUNK) void unproj_count_kernel(UnprojArgs a
   }
   bool keep = false;
   if (p < a.HW) keep = unproj_keep(a, b, p, a.x[((size_t)b * a.C) * a.HW + p]);
-  const unsigned long long m = __ballot(keep);
-  if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6] = __popcll(m);
+  chunk_post(keep, wcnt);
   __syncthreads();
-  if (threadIdx.x == 0) a.chunk[c] = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+  if (threadIdx.x == 0) a.chunk[c] = chunk_total(wcnt);
 }
 
 __global__ __launch_bounds__(UNPROJ_SCAN_THREADS) void unproj_scan_kernel(UnprojArgs a) {
-  __shared__ int wsum[UNPROJ_SCAN_THREADS / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int n = a.B * a.cpv;
-  long long carry = 0;   // rows before this tile; unproj_shape_ok keeps every base in an int
-  for (int t0 = 0; t0 < n; t0 += UNPROJ_SCAN_THREADS * UNPROJ_SCAN_PER_THREAD) {
-    const int i0 = t0 + tid * UNPROJ_SCAN_PER_THREAD;
-    int c[UNPROJ_SCAN_PER_THREAD], cnt = 0;
-#pragma unroll
-    for (int k = 0; k < UNPROJ_SCAN_PER_THREAD; ++k) {
-      c[k] = i0 + k < n ? a.chunk[i0 + k] : 0;
-      cnt += c[k];
-    }
-    int inc = cnt;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int v = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += v;
-    }
-    if (lane == 63) wsum[wv] = inc;
-    __syncthreads();
-    int before = 0, total = 0;
-    for (int k = 0; k < UNPROJ_SCAN_THREADS / 64; ++k) {
-      before += k < wv ? wsum[k] : 0;
-      total += wsum[k];
-    }
-    long long base = carry + before + (inc - cnt);
-#pragma unroll
-    for (int k = 0; k < UNPROJ_SCAN_PER_THREAD; ++k) {
-      const int i = i0 + k;
-      if (i < n) {
-        a.chunk[i] = (int)base;
-        if (i % a.cpv == 0) a.offsets[i / a.cpv] = base;
-      }
-      base += c[k];
-    }
-    carry += total;
-    __syncthreads();   // wsum is rewritten by the next tile
-  }
-  if (tid == 0) a.offsets[a.B] = carry;
+  // unproj_shape_ok keeps every base and the total below 2^31, so the scan's int carry needs no widening
+  const int total = block_exclusive_scan(a.chunk, a.B * a.cpv);   // its last barrier: the bases are visible
+  for (int b = threadIdx.x; b < a.B; b += UNPROJ_SCAN_THREADS) a.offsets[b] = a.chunk[(size_t)b * a.cpv];
+  if (threadIdx.x == 0) a.offsets[a.B] = total;
 }
 
 __global__ __launch_bounds__(UNPROJ_CHUNK) void unproj_scatter_kernel(UnprojArgs a) {
   __shared__ int wcnt[UNPROJ_CHUNK / 64];
   const int c = blockIdx.x, b = c / a.cpv, p = (c - b * a.cpv) * UNPROJ_CHUNK + threadIdx.x;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const float* xb = a.x + ((size_t)b * a.C) * a.HW;
   float code = 0.f;
   bool keep = false;
@@ -129,14 +90,11 @@ __global__ __launch_bounds__(UNPROJ_CHUNK) void unproj_scatter_kernel(UnprojArgs
     code = xb[p];
     keep = unproj_keep(a, b, p, code);
   }
-  const unsigned long long m = __ballot(keep);
-  if (lane == 0) wcnt[wv] = __popcll(m);
+  const unsigned long long m = chunk_post(keep, wcnt);
   __syncthreads();
   if (!keep) return;
   const float rd = unproj_distance(code);
-  int rank = __popcll(m & ((1ull << lane) - 1ull));
-  for (int k = 0; k < wv; ++k) rank += wcnt[k];
-  const size_t row = (size_t)a.chunk[c] + rank;
+  const size_t row = (size_t)a.chunk[c] + chunk_rank(m, wcnt);
   const int i = p / a.W, j = p - i * a.W;
   const double2 tz = a.trig[j], te = a.trig[(size_t)a.W + i];
   const double rdd = (double)rd;
@@ -236,8 +194,7 @@ int sdp_range_unproject(const float* x, int B, int C, int H, int W, int geometry
   hipLaunchKernelGGL(sdp::unproj_count_kernel, dim3(n_chunks), dim3(sdp::UNPROJ_CHUNK), 0, st, a);
   hipLaunchKernelGGL(sdp::unproj_scan_kernel, dim3(1), dim3(sdp::UNPROJ_SCAN_THREADS), 0, st, a);
   hipLaunchKernelGGL(sdp::unproj_scatter_kernel, dim3(n_chunks), dim3(sdp::UNPROJ_CHUNK), 0, st, a);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : sdp_fail(std::string("sdp_range_unproject: ") + hipGetErrorString(e));
+  return sdp::launch_status("sdp_range_unproject");
 }
 
 }  // extern "C"

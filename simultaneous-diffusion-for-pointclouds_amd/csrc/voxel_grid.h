@@ -7,9 +7,9 @@
 
 #include <hip/hip_runtime.h>
 
-namespace sdp {
+#include "radix_sort.h"
 
-constexpr int VOX_HDR_PASSES = 8;            // = VOXEL_LABEL_PASSES of voxel_grid.hip, the longer of its two sorts
+namespace sdp {
 
 struct VoxHdr {
   float org[3];
@@ -17,8 +17,8 @@ struct VoxHdr {
   unsigned long long nx, ny;    // key = ix + nx*iy + nx*ny*iz
   long long dims[3];            // nx, ny, nz as reported (each clamped to 2^62 when the grid is too large)
   int key_bits, too_large, used, m;
-  int src[2][VOX_HDR_PASSES + 1];   // [voxel keys | label keys]: the buffer pass p reads
-  int active[2][VOX_HDR_PASSES];
+  int label_bits;               // width of the (voxel row, label) keys, known once m is
+  RadixState sort[2];           // [voxel keys | label keys]
   float lo[3], hi[3];           // bounds of the finite points (float32), for the consumers of the cell grid
 };
 

@@ -38,6 +38,13 @@ from . import _lib
 GEOMETRY = {"dataset": 0, "sampler": 1}
 
 
+def _workspace(entry, *args, device):
+    """The uint8 workspace tensor whose size the ``sdp_<entry>_workspace_size`` entry reports for ``args``."""
+    n = _lib.SZ()
+    _lib.check(getattr(_lib.lib(), f"sdp_{entry}_workspace_size")(*args, _lib.C.byref(n)), f"{entry}_ws")
+    return torch.empty(n.value, dtype=torch.uint8, device=device)
+
+
 def _mask_u8(m, shape, what):
     if m is None:
         return None
@@ -72,10 +79,8 @@ def range_image_to_point_cloud(x, origins=None, poses=None, keep=None, exist=Non
     keep = _mask_u8(keep, (B, H, W), "keep")
     exist = _mask_u8(exist, (H, W), "exist")
     L = _lib.lib()
-    n = _lib.SZ()
-    _lib.check(L.sdp_range_unproject_workspace_size(B, H, W, _lib.C.byref(n)), "range_unproject_ws")
+    ws = _workspace("range_unproject", B, H, W, device=dev)
     with torch.cuda.device(dev):
-        ws = torch.empty(n.value, dtype=torch.uint8, device=dev)
         points = torch.empty(B * H * W, 4, dtype=torch.float64, device=dev)
         pixel = torch.empty(B * H * W, dtype=torch.int32, device=dev) if return_pixel else None
         offsets = torch.empty(B + 1, dtype=torch.int64, device=dev)
@@ -131,10 +136,8 @@ def voxel_grid_subsample(points, features=None, classes=None, sampleDl=0.1, cent
         c = classes.reshape(n, -1).to(torch.int32).contiguous()
         ldim = c.shape[1]
     L = _lib.lib()
-    nb = _lib.SZ()
-    _lib.check(L.sdp_voxel_grid_workspace_size(n, _lib.C.byref(nb)), "voxel_grid_ws")
+    ws = _workspace("voxel_grid", n, device=dev)
     with torch.cuda.device(dev):
-        ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
         op = torch.empty(n, 3, dtype=torch.float32, device=dev)
         of = torch.empty(n, fdim, dtype=torch.float32, device=dev) if f is not None else None
         oc = torch.empty(n, ldim, dtype=torch.int32, device=dev) if c is not None else None
@@ -188,10 +191,8 @@ def _nn_launch(q, t, max_dist, cell, center):
         c64 = torch.as_tensor(center, dtype=torch.float64).to(dev).reshape(3).contiguous()
     L = _lib.lib()
     nq, nt = q.shape[0], t.shape[0]
-    nb = _lib.SZ()
-    _lib.check(L.sdp_cloud_nn_workspace_size(nq, nt, _lib.C.byref(nb)), "cloud_nn_ws")
+    ws = _workspace("cloud_nn", nq, nt, device=dev)
     with torch.cuda.device(dev):
-        ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
         d2 = torch.empty(nq, dtype=torch.float64, device=dev)
         idx = torch.empty(nq, dtype=torch.int32, device=dev)
         info = torch.empty(8, dtype=torch.int64, device=dev)
@@ -252,10 +253,8 @@ def nearest_neighbours(query, target, max_dist, cell=None, center=None):
 def _nn_stats_launch(d2, q, thresholds, max_dist):
     L = _lib.lib()
     n, T = q.shape[0], len(thresholds)
-    nb = _lib.SZ()
-    _lib.check(L.sdp_cloud_nn_stats_workspace_size(n, _lib.C.byref(nb)), "cloud_nn_stats_ws")
+    ws = _workspace("cloud_nn_stats", n, device=q.device)
     with torch.cuda.device(q.device):
-        ws = torch.empty(nb.value, dtype=torch.uint8, device=q.device)
         out = torch.empty(5 + T, dtype=torch.float64, device=q.device)
         thr = (_lib.D * max(T, 1))(*thresholds)
         _lib.check(L.sdp_cloud_nn_stats(_lib.ptr(d2) if n else None, _lib.ptr(q) if n else None, q.shape[1], n, thr, T,

@@ -56,6 +56,8 @@ SIGS = {
     "sdpk_end_conv_backward": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, P]),
     "sdpk_head_wgrad_part_floats": (SZ, [I, I, I]),
     "sdpk_range_sky_scan": (I, [P, I, I, P, P, P]),
+    "sdpk_block_scan": (I, [P, I, P, P]),
+    "sdpk_radix_sort": (I, [P, P, P, P, P, C.c_int64, P, P, I, P]),
 }
 
 _bound = None

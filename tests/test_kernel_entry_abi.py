@@ -20,7 +20,7 @@ def declared():
 
 def test_library_exports_every_declared_kernel_entry():
     d = declared()
-    assert len(d) == 21, d
+    assert len(d) == 23, d
     out = subprocess.run(["nm", "-D", "--defined-only", LIB], capture_output=True, text=True, check=True).stdout
     exported = set(re.findall(r" T (sdpk_\w+)", out))
     assert exported == set(d), (sorted(exported - set(d)), sorted(set(d) - exported))
