@@ -22,6 +22,11 @@
 //           taps 0..3 transform raw -> patch[(k+1)&1] (consumer prologue: InstanceNorm++
 //           affine and/or ELU, zero padding, bf16 hi/lo split) and the taps 4..8 issue the
 //           LDS-DMA of chunk k+2 into raw.
+//   tail  : the tap schedule of the bf16 modes (do_chunk9) peels its last two chunks at compile time: the
+//           second-to-last issues no LDS-DMA (there is no chunk k+2), the last no transform and no weight loads
+//           of a next chunk either, and the direct epilogue follows it without a wait or a barrier.  The older
+//           do_chunk loop (exact fp32, 1x1, the transposed data gradient) still runs its fillers in every chunk;
+//           past the last chunk they touch only dead buffers.
 //   weights: pre-arranged on the device in MFMA fragment order (train_aux.hip), streamed from L2 into VGPRs
 //           a tap or more ahead (buffer_load_b128 with a scalar per-(chunk, tap) offset).
 //   S2     : the K loop runs 4 input phases x Cin/32 chunks of 4 taps each (2 x 2 of the 3 x 3 patch positions,
@@ -69,6 +74,14 @@ namespace sdp {
 
 #ifndef SDP_ROWS      // the forward 8 x 16 tiles' A fragments as a ring of patch rows, taps kw-major (ROWS below);
 #define SDP_ROWS 1    // 0 (build-time A/B) = the per-tap fragments ca / cb of every other tile shape
+#endif
+
+#ifndef SDP_TAIL      // the tap schedule's K loop (do_chunk9) ends in a peeled pair of chunks that stages nothing past the
+#define SDP_TAIL 1    // last chunk (TAIL below); 0 (build-time A/B) = every chunk runs the steady body, its fillers dead
+#endif                // in the last two
+
+#ifndef SDP_DGRAD16_TAPS   // A/B (build-time): the IO16 data gradient on the tap schedule -- measured slower,
+#define SDP_DGRAD16_TAPS 0    // bf16-tape training 181.0-181.5 -> 177.6-177.8 image-steps/s (profiles/experiments/r06_dgrad16_taps_ab.log)
 #endif
 
 #ifdef SDP_TIMING   // tools/conv_bench: per-workgroup phase clocks of wave 0 into a.dbg
@@ -257,6 +270,10 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
   constexpr int XT = NT >= 4 ? 4 : NT;            // taps that carry the transform of the next chunk
   // the forward 3x3 on 8 x 16 tiles: kw-major taps on a ring of patch-row A fragments (rows_pos, rows_read)
   constexpr bool ROWS = SDP_ROWS && SH == 16 && !S2 && NT == 9 && TC == 16 && NJ == 2 && !TRANS;
+  // the launches whose K loop is the tap schedule (do_chunk9), and of those the ones that end it in the peeled pair
+  constexpr bool TAPS9 = S2 || (MODE != MODE_F32 && NT == 9 && (!TRANS || (IO16 && SDP_DGRAD16_TAPS)));
+  constexpr bool TAILED = SDP_TAIL && TAPS9;
+  constexpr bool STAGED_EPI = TC >= 32 && NW == 4 && SH == 16;   // a.dact can send the launch to the LDS-staged epilogue
   __shared__ __attribute__((aligned(16))) char lds[T::LDS_BYTES];
   char* const raw = lds + 2 * T::PATCH_BYTES;
 
@@ -385,7 +402,7 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
   // S2: the chunks run (phase 0, phase 1) x channel chunks, then (phase 2, phase 3) x channel chunks (phase = 2 x row
   // parity + column parity), so the phase -- the tap set -- is a compile-time constant of the main loop's two chunk
   // parities; the phase moves the patch by (row parity, column parity) full-resolution pixels.  Chunks past the
-  // last one (the dead transform / DMA of the loop's tail) repeat the last
+  // last one (staged only by do_chunk, and by the tap schedule built with SDP_TAIL = 0) repeat the last
   auto chunk_cc = [&](int c) __attribute__((always_inline)) {
     if constexpr (S2) return (c >= 2 * nck ? c - 2 * nck : c) >> 1;
     else return c;
@@ -457,11 +474,13 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
   // later, and the weight loads issued after its DMA -- which complete in issue order with it --
   // are waited for two taps later, before their MFMAs
   const i32x4 irs_o = buffer_desc(inb, (uint32_t)(a.H * a.W * Cin * ES));
+  // the LDS byte address of the wave's 1-KiB raw slot of unit 0 (unit k: + k * NTH * 16), wave-uniform: one scalar,
+  // where a per-unit address held a 64-bit register pair across the K loop
+  const uint32_t raw_wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)(raw + (tid & ~63) * 16));
   auto load_unit_o = [&](auto kc, int chunk) __attribute__((always_inline)) {
     constexpr int k = decltype(kc)::value;
     if constexpr (SDP_KO & 1) return;
-    const uint32_t base = (uint32_t)(uintptr_t)(raw + ((tid & ~63) + k * NTH) * 16);
-    dma16_lds_opaque(irs_o, base, uoff[k], chunk_soff(chunk));
+    dma16_lds_opaque(irs_o, raw_wave + k * NTH * 16, uoff[k], chunk_soff(chunk));
   };
   // transform staging unit k of raw into patch buffer PB
   // transform of staging unit k: raw (fp32, landed by this thread's own DMA) -> patch buffer PB
@@ -748,6 +767,8 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
   static_assert(NQ <= NBLK / 2 && 2 * NWL <= NBLK, "the tap's fillers fit its blocks");
   using I0 = std::integral_constant<int, 0>;
   using I1 = std::integral_constant<int, 1>;
+  using I2 = std::integral_constant<int, 2>;
+  using I3 = std::integral_constant<int, 3>;
   // one A fragment: pixel group i of half s of the tap at patch position pos = 3 kh + kw, hi (LO = 0) or lo part
   auto read_a1 = [&](const char* pat, auto pos_c, auto s_c, auto i_c, auto lo_c) __attribute__((always_inline)) {
     constexpr int pos = decltype(pos_c)::value, s = decltype(s_c)::value, i = decltype(i_c)::value;
@@ -766,8 +787,12 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
     bq[J][nj >> 1][2 * (nj & 1) + part] = make_uint4(v.x, v.y, v.z, v.w);
   };
   // (PHS: the input phase of the chunk, S2 only -- the patch positions of its taps)
-  auto do_chunk9 = [&](auto parity, auto phase_c, int chunk) __attribute__((always_inline)) {
-    constexpr int P = decltype(parity)::value, PHS = decltype(phase_c)::value;
+  // TAIL: 0 = the steady body; 1 = the second-to-last chunk -- no chunk + 2 exists, so no LDS-DMA and no (scale, shift)
+  // rows for it; 2 = the last chunk -- no chunk + 1 either: no raw reads, no transform, no weight loads of a next
+  // chunk's first taps, and no closing barrier in front of a direct epilogue (which touches no LDS).  The removed
+  // fillers leave their blocks bare; the MFMAs, the A-fragment reads and the ring slots are those of the steady body.
+  auto do_chunk9 = [&](auto parity, auto phase_c, int chunk, auto tail_c) __attribute__((always_inline)) {
+    constexpr int P = decltype(parity)::value, PHS = decltype(phase_c)::value, TAIL = decltype(tail_c)::value;
     const char* pat = lds + P * T::PATCH_BYTES;
     bf16x8 ca[2][4], cb[2][4];   // [hi, lo][i]: half s = 0 / s = 1 of the current tap
     bf16x8 ar[2][ROWS ? ROWS_SLOTS : 1];   // ROWS: [hi, lo][rows_slot] instead, the patch rows of the current kw
@@ -786,7 +811,8 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
         if constexpr (MODE == MODE_F32X3) ca[1][i] = read_a1(pat, POS0{}, I0{}, i, I1{});
       }
     });
-    load_ss(std::integral_constant<int, P>{}, chunk_cc(min(chunk + 2, nchunks - 1)));   // buffer P: chunk-1's, free
+    if constexpr (TAIL == 0)
+      load_ss(std::integral_constant<int, P>{}, chunk_cc(min(chunk + 2, nchunks - 1)));   // buffer P: chunk-1's, free
     static_for<0, NT>([&](auto tap_c) {
       constexpr int tap = decltype(tap_c)::value;
       constexpr int DIST = NBUF - 1;                     // weight prefetch distance in taps; ring slot = tap % NBUF
@@ -910,7 +936,7 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
         constexpr int blk = decltype(blk_c)::value;
         constexpr int s = blk / (4 * NJ), nj = (blk / 4) % NJ, i = blk & 3, mb = 4 * s + i;
         // ---- fillers that feed this tap: raw reads first (the transform waits on them)
-        if constexpr (blk < UN) xr[blk] = xform_load(std::integral_constant<int, U0 + blk>{});
+        if constexpr (TAIL < 2 && blk < UN) xr[blk] = xform_load(std::integral_constant<int, U0 + blk>{});
         // ---- the block's MFMAs
         {
           const uint4 h4 = bq[CUR][nj >> 1][2 * (nj & 1)], l4 = bq[CUR][nj >> 1][2 * (nj & 1) + 1];
@@ -949,53 +975,61 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
           constexpr int q = blk, ii = MODE == MODE_F32X3 ? (q >> 1) : q, lo = MODE == MODE_F32X3 ? (q & 1) : 0;
           cb[lo][ii] = read_a1(pat, POS{}, I1{}, std::integral_constant<int, ii>{}, std::integral_constant<int, lo>{});
         }
-        if constexpr ((blk & 1) && (blk >> 1) < NWL)   // tap + 2's weights
+        if constexpr ((blk & 1) && (blk >> 1) < NWL && (TAIL < 2 || tap + DIST < NT))   // tap + 2's weights
           load_b1(std::integral_constant<int, NXT>{}, std::integral_constant<int, (blk >> 1)>{}, wchunk, wtap);
         if constexpr (!ROWS && tap + 1 < NT && blk >= NBLK / 2 && blk < NBLK / 2 + NQ) {   // tap + 1's half-0 fragments
           constexpr int q = blk - NBLK / 2, ii = MODE == MODE_F32X3 ? (q >> 1) : q, lo = MODE == MODE_F32X3 ? (q & 1) : 0;
           ca[lo][ii] = read_a1(pat, POSN{}, I0{}, std::integral_constant<int, ii>{},
                                std::integral_constant<int, lo>{});
         }
-        static_for<0, Q>([&](auto q_c) {   // transform stages dealt to this block
+        static_for<0, (TAIL < 2 ? Q : 0)>([&](auto q_c) {   // transform stages dealt to this block
           constexpr int q = decltype(q_c)::value;
           if constexpr (XP::stage_blk(q, Q, NBLK) == blk) {
             if constexpr (COPY) stage(std::integral_constant<int, q>{}, std::integral_constant<int, 0>{});
             else stage(std::integral_constant<int, q / XP::NSTG>{}, std::integral_constant<int, q % XP::NSTG>{});
           }
         });
-        if constexpr (UN > 0 && blk >= NBLK - UN)   // the DMA of a transformed unit (its raw slot was read)
+        if constexpr (TAIL == 0 && UN > 0 && blk >= NBLK - UN)   // the DMA of a transformed unit (its raw slot was read)
           load_unit_o(std::integral_constant<int, U0 + blk - (NBLK - UN)>{}, chunk + 2);
         __builtin_amdgcn_sched_barrier(0);
       });
     });
-    // patch[P] free for chunk+2's transform, patch[1-P] complete (see do_chunk)
-    __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0)
-    if constexpr (!(SDP_KO & 8)) __builtin_amdgcn_s_barrier();
+    // patch[P] free for chunk+2's transform, patch[1-P] complete (see do_chunk).  After the last chunk nothing was
+    // written: the barrier stays only where the LDS-staged epilogue, which reuses the buffers, can follow
+    if constexpr (TAIL < 2 || STAGED_EPI) {
+      __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0)
+      if constexpr (!(SDP_KO & 8)) __builtin_amdgcn_s_barrier();
+    }
   };
   // do_chunk's 2-slot weight ring alternates with the chunk parity, which assumes an odd tap count; the tap
   // schedule's slot is tap % NBUF, the same in every chunk when NBUF divides the tap count (9 = 3 x 3, S2: 4 = 2 x 2)
   static_assert(NT % 2 == 1 || (S2 && NT % NBUF == 0), "weight-ring slots repeat from chunk to chunk");
   // (the data-gradient launches keep do_chunk: in bf16 training the tap schedule measured 3-5 % slower
   // on them, profiles/experiments/r05_train_kernel_stats_ab.log)
-#ifndef SDP_DGRAD16_TAPS   // A/B (build-time): the IO16 data gradient on the tap schedule -- measured slower,
-#define SDP_DGRAD16_TAPS 0    // bf16-tape training 181.0-181.5 -> 177.6-177.8 image-steps/s (profiles/experiments/r06_dgrad16_taps_ab.log)
-#endif
   if constexpr (S2) {
     static_assert(MODE != MODE_F32 && NT % NBUF == 0, "4x4 stride-2: the tap schedule of the bf16 modes");
     static_assert(XP::max_count() * PPU * XP::NSTG <= 2 * (NBLK - 2), "at most two transform stages per block");
     for (int chunk = 0; chunk < 2 * nck; chunk += 2) {   // row parity 0: column parity = chunk parity
-      do_chunk9(I0{}, I0{}, chunk);
-      do_chunk9(I1{}, I1{}, chunk + 1);
+      do_chunk9(I0{}, I0{}, chunk, I0{});
+      do_chunk9(I1{}, I1{}, chunk + 1, I0{});
     }
-    for (int chunk = 2 * nck; chunk < nchunks; chunk += 2) {   // row parity 1
-      do_chunk9(I0{}, std::integral_constant<int, 2>{}, chunk);
-      do_chunk9(I1{}, std::integral_constant<int, 3>{}, chunk + 1);
+    for (int chunk = 2 * nck; chunk < nchunks - (TAILED ? 2 : 0); chunk += 2) {   // row parity 1
+      do_chunk9(I0{}, I2{}, chunk, I0{});
+      do_chunk9(I1{}, I3{}, chunk + 1, I0{});
     }
-  } else if constexpr (MODE != MODE_F32 && NT == 9 && (!TRANS || (IO16 && SDP_DGRAD16_TAPS))) {
+    if constexpr (TAILED) {   // the (phase 2, phase 3) pair of the last channel chunk
+      do_chunk9(I0{}, I2{}, nchunks - 2, I1{});
+      do_chunk9(I1{}, I3{}, nchunks - 1, I2{});
+    }
+  } else if constexpr (TAPS9) {
     static_assert(XP::max_count() * PPU * XP::NSTG <= 2 * (NBLK - 2), "at most two transform stages per block");
-    for (int chunk = 0; chunk < nchunks; chunk += 2) {   // nchunks is even (Cin % 64 == 0)
-      do_chunk9(I0{}, I0{}, chunk);
-      do_chunk9(I1{}, I0{}, chunk + 1);
+    for (int chunk = 0; chunk < nchunks - (TAILED ? 2 : 0); chunk += 2) {   // nchunks is even (Cin % 64 == 0)
+      do_chunk9(I0{}, I0{}, chunk, I0{});
+      do_chunk9(I1{}, I0{}, chunk + 1, I0{});
+    }
+    if constexpr (TAILED) {   // the last two chunks (the only two of a 64-channel input)
+      do_chunk9(I0{}, I0{}, nchunks - 2, I1{});
+      do_chunk9(I1{}, I0{}, nchunks - 1, I2{});
     }
   } else {
     for (int chunk = 0; chunk < nchunks; chunk += 2) {
@@ -1016,7 +1050,9 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
     // values (one per fragment mb) of each of its 16 channels; the 128-pixel group of a channel spans
     // the 16 lanes of a DPP row -> per-lane two-pass (mean, M2), then Chan merges over the row by
     // quad_perm / row_half_mirror / row_mirror moves.
-    __builtin_amdgcn_s_waitcnt(0);   // the last (dead) DMA may still be landing in raw
+    // do_chunk's last (dead) DMA may still be landing in raw; the peeled tap schedule leaves nothing in flight that
+    // the tile does not need, and the epilogue waits for its own loads only
+    if constexpr (!TAILED) __builtin_amdgcn_s_waitcnt(0);
     const int Ho = a.H, Wo = a.W;
     const size_t bo = (size_t)b * Ho * Wo * Cout;
     const int img_bytes = Ho * Wo * Cout * ES;
@@ -1188,7 +1224,9 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
     // row segment and Cout 16 nj + l % 16 of the wave's 64: every wave store writes four 64-B runs
     // of channels.  ConvMeanPool pairs registers r, r+1 (columns) and fragments mb, mb + TC/16
     // (rows); the 128-pixel InstanceNorm++ group of a channel spans the 4 lanes l % 16 + 16q.
-    __builtin_amdgcn_s_waitcnt(0);   // the last (dead) DMA may still be landing in raw
+    // do_chunk's last (dead) DMA may still be landing in raw; the peeled tap schedule leaves nothing in flight that
+    // the tile does not need, and the epilogue waits for its own loads only
+    if constexpr (!TAILED) __builtin_amdgcn_s_waitcnt(0);
     const int Ho = (POOL || S2) ? a.H / 2 : a.H, Wo = (POOL || S2) ? a.W / 2 : a.W;
     const int de = S2 ? 1 : d;                       // pixel step of the output (S2: the tile's own half-resolution grid)
     const size_t bo = (size_t)b * Ho * Wo * Cout;
@@ -1375,7 +1413,9 @@ __global__ __launch_bounds__(64 * NW, NJ == 2 ? 2 : 1) void conv_mfma_kernel(Con
     // 1 KiB (Cout 256) or two 512-B rows -- with bias, 2x2 mean-pool, residual, bilinear
     // upsample-add, the CRP second output, ELU and the InstanceNorm++ statistics applied on
     // the way.
-    __builtin_amdgcn_s_waitcnt(0);   // the last (dead) DMA may still be landing in raw
+    // do_chunk's last (dead) DMA may still be landing in raw; the peeled tap schedule leaves nothing in flight that
+    // the tile does not need, and the epilogue waits for its own loads only
+    if constexpr (!TAILED) __builtin_amdgcn_s_waitcnt(0);
     __syncthreads();
     constexpr int SROW = T::NTILE + 8;               // staged row stride (floats): conflict-free writes
     constexpr int SP = WM * 64;                      // staged pixels per half
