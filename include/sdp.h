@@ -33,6 +33,8 @@
  *   sdp_voxel_grid         voxel-grid subsampling, DEVICE memory, barycenters  .../grid_subsampling/grid_subsampling.cpp:46-102
  *   sdp_cloud_nn           exact nearest neighbour within a radius, cloud to cloud   (no counterpart: MeasureResults/ scores
  *   sdp_cloud_nn_stats     Chamfer / precision / recall sums of one direction         images only, per-pixel MAE)
+ *   sdp_voxel_iou          voxel occupancy / semantic confusion matrix of two clouds  MeasureResults/SceneCompleter.py:256-270
+ *                                                                             (the cloud it hands to a metrics.iou it does not ship)
  */
 #ifndef SDP_H
 #define SDP_H
@@ -379,6 +381,53 @@ int sdp_cloud_nn_stage_events(void* const* events);
 int sdp_cloud_nn_stats_workspace_size(int64_t n, size_t* bytes);
 int sdp_cloud_nn_stats(const double* nn_d2, const double* q, int qstride, int64_t n, const double* thresholds, int nthr,
                        double max_dist, double* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- voxel occupancy and semantic IoU between two clouds on the DEVICE (csrc/voxel_iou.hip) ----
+ * sdp_voxel_iou puts cloud A (the truth) and cloud B (the prediction) on ONE fixed grid and counts, per pair of
+ * voxel states, the voxels of the grid: the confusion matrix that completion IoU and per-class IoU come from.
+ *   Grid: origin float64 [3] (HOST) the low corner, voxel > 0 a float64 size, dims = (nx, ny, nz) (HOST int64 [3]),
+ *     each >= 1, nx*ny*nz <= 2^40.
+ *   Cell of a point: per axis i = floor((p - origin) / voxel) in float64 -- one subtraction, one IEEE division, one
+ *     floor, each rounded once; no reciprocal, no FMA.  Cell key = ix + nx*iy + nx*ny*iz.
+ *   A point is USED iff its three coordinates are finite, 0 <= i < n on every axis (tested on the floored double
+ *     before any integer conversion: NaN, +-inf and 1e300 drop out), its label lies in [0, C) and its cell is valid.
+ *   Labels: a_labels / b_labels int32 [n] (DEVICE) or NULL = every point has label 0; C = num_classes in [1, 64].
+ *     A point whose label is outside [0, C) is not used; such points are counted (info[4], info[5]) whatever their
+ *     coordinates.  The label of an occupied voxel is the label most of its used points carry; among equal counts
+ *     the SMALLEST label value (sdp_voxel_grid's device rule).
+ *   valid: DEVICE uint8 [nz][ny][nx] (key order) or NULL = every cell valid.  A cell with 0 takes no part anywhere
+ *     and the points in it are not used.  A mask requires nx*ny*nz <= 2^31.
+ *   Result: confusion int64 [(C+1)*(C+1)] (DEVICE), row = state in A, column = state in B; state 0 = empty, state
+ *     1 + c = occupied with majority label c.  confusion[0][0] = valid cells - |A u B|, so the matrix sums to the
+ *     number of valid cells.
+ *   Optional outputs (DEVICE, NULL = skip; capacity na resp. nb rows, rows >= m are not written): the occupied
+ *     cells of each side in ascending key, a_cells int64 [m_a], their majority labels a_cell_labels int32 [m_a] and
+ *     their used-point counts a_cell_counts int32 [m_a]; the same for B.
+ *   info int64 [8] (DEVICE) = {m_a, m_b, points used a, points used b, a points with a bad label, b points with a
+ *     bad label, |A n B|, valid cells}.
+ * Inputs (DEVICE): a float64 [na][astride], b float64 [nb][bstride], xyz first, stride 3 or 4; 0 <= na, nb <= 2^30,
+ * an empty cloud is valid.  Bad dims, voxel <= 0 or not finite, a non-finite origin, C outside [1, 64], a mask with
+ * more than 2^31 cells and a grid of more than 2^40 cells fail the call (sdp_last_error) and write nothing.
+ * Per cloud: compaction of the used points in point order, a stable radix sort of the keys cell * 64 + label with
+ * exactly ceil((ceil(log2(cells)) + 6) / 8) passes, segment heads by cell, one thread per voxel for the longest
+ * label run.  Then every cell of A is searched in B's cells and every cell of B in A's; workgroups count their
+ * pairs in LDS and one workgroup adds the partials in a fixed order.  All on `stream`, no host synchronisation, no
+ * workgroup waits for another; the only atomics are integer LDS adds whose sums do not depend on their order:
+ * every count is exact and two calls give identical bits.
+ * workspace: 16-byte aligned, sdp_voxel_iou_workspace_size(na, nb, num_classes) bytes.                          */
+int sdp_voxel_iou_workspace_size(int64_t na, int64_t nb, int num_classes, size_t* bytes);
+int sdp_voxel_iou(const double* a, int64_t na, int astride, const int32_t* a_labels /* or NULL */,
+                  const double* b, int64_t nb, int bstride, const int32_t* b_labels /* or NULL */,
+                  const double* origin /* HOST [3] */, double voxel, const int64_t* dims /* HOST [3] */,
+                  int num_classes, const uint8_t* valid /* DEVICE or NULL */,
+                  int64_t* confusion /* DEVICE [(C+1)*(C+1)] */,
+                  int64_t* a_cells, int32_t* a_cell_labels, int32_t* a_cell_counts,   /* each optional, capacity na */
+                  int64_t* b_cells, int32_t* b_cell_labels, int32_t* b_cell_counts,   /* each optional, capacity nb */
+                  int64_t* info /* DEVICE [8] */, void* workspace, size_t workspace_bytes, void* stream);
+/* Measurement hook (tools/voxel_iou_bench.py): events = HOST array of 6 hipEvent_t that every later sdp_voxel_iou
+ * of this thread records on its stream -- before the first kernel, then after the keys, the sorts, the segment
+ * heads, the votes and the comparison; NULL switches it off.                                                    */
+int sdp_voxel_iou_stage_events(void* const* events);
 
 #ifdef __cplusplus
 }

@@ -82,6 +82,10 @@ _SIGS = {
     "sdp_cloud_nn_stage_events": (I, [C.POINTER(P)]),
     "sdp_cloud_nn_stats_workspace_size": (I, [C.c_int64, C.POINTER(SZ)]),
     "sdp_cloud_nn_stats": (I, [P, P, I, C.c_int64, C.POINTER(D), I, D, P, P, SZ, P]),
+    "sdp_voxel_iou_workspace_size": (I, [C.c_int64, C.c_int64, I, C.POINTER(SZ)]),
+    "sdp_voxel_iou": (I, [P, C.c_int64, I, P, P, C.c_int64, I, P, C.POINTER(D), D, C.POINTER(C.c_int64), I, P, P,
+                          P, P, P, P, P, P, P, P, SZ, P]),
+    "sdp_voxel_iou_stage_events": (I, [C.POINTER(P)]),
     "sdp_langevin_step": (I, [P, P, P, P, P, U64, U64, F, F, F, I, I, I, I, P, P, P]),
     "sdp_axpy_step": (I, [P, P, F, P, P, P, F, I, P]),
     "sdp_merge_workspace_size": (I, [I, I, I, I, C.POINTER(SZ)]),

@@ -25,6 +25,12 @@ ascending voxel key.
 ``nearest_neighbours`` / ``cloud_metrics`` score one such cloud against another on the device
 (``sdp_cloud_nn`` / ``sdp_cloud_nn_stats``, csrc/cloud_nn.hip): the exact nearest target within a radius
 for every point, and from it Chamfer distance, accuracy / completeness and precision / recall / F-score.
+
+``voxel_confusion`` / ``voxel_iou`` grade a cloud the way scene completion is graded (``sdp_voxel_iou``,
+csrc/voxel_iou.hip): both clouds on one fixed grid (``SSC_GRID``: SemanticKITTI-SSC's 256 x 256 x 32 voxels of
+0.2 m), the majority label of every occupied voxel, the confusion matrix of the voxel states, and from it
+(``iou_from_confusion``) the completion IoU and the per-class IoU / mIoU.  ``volume_to_cloud`` turns a dense
+ground-truth label volume into the labelled cloud these take.
 """
 from __future__ import annotations
 
@@ -329,6 +335,139 @@ def cloud_metrics(a, b, max_dist, thresholds=(0.1, 0.2, 0.5), cell=None):
     _, rows = cloud_distance_stats(a, b, max_dist, thr, cell)
     ab, ba = rows.tolist()
     return metrics_from_stats(ab, ba, thr)
+
+
+SSC_GRID = {"origin": (0.0, -25.6, -2.0), "voxel": 0.2, "dims": (256, 256, 32)}   # SemanticKITTI-SSC, 51.2 x 51.2 x 6.4 m
+
+
+def _grid_args(origin, voxel, dims, num_classes, what):
+    org = [float(v) for v in np.asarray(origin, dtype=np.float64).reshape(-1)]
+    if len(org) != 3 or not all(np.isfinite(org)):
+        raise ValueError(f"{what}: origin must be three finite numbers")
+    voxel = float(voxel)
+    if not voxel > 0 or not np.isfinite(voxel):
+        raise ValueError(f"{what}: voxel must be > 0 and finite")
+    d = [int(v) for v in dims]
+    if len(d) != 3 or any(v < 1 for v in d) or any(int(v) != v for v in dims):
+        raise ValueError(f"{what}: dims must be three integers >= 1")
+    if d[0] * d[1] * d[2] > 2 ** 40:
+        raise ValueError(f"{what}: a grid of {d[0]} x {d[1]} x {d[2]} cells exceeds 2^40 cells")
+    if not 1 <= int(num_classes) <= 64:
+        raise ValueError(f"{what}: num_classes must be in [1, 64]")
+    return org, voxel, d, int(num_classes)
+
+
+def _labels_i32(t, n, dev, what):
+    if t is None:
+        return None
+    if not torch.is_tensor(t) or not t.is_cuda or t.device != dev or tuple(t.shape) != (n,) or \
+            t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise ValueError(f"{what} must be a cuda integer [{n}] tensor on the clouds' device")
+    return t.to(torch.int32).contiguous()
+
+
+def voxel_confusion(truth, pred, origin, voxel, dims, truth_labels=None, pred_labels=None, num_classes=1,
+                    valid=None, return_cells=False):
+    """The confusion matrix of voxel states between clouds ``truth`` and ``pred`` on one fixed grid, on the device
+    (``sdp_voxel_iou``, csrc/voxel_iou.hip; the contract stands in include/sdp.h).
+
+    truth, pred: cuda [n,3] or [n,4] (xyz first), float64 (float32 is widened).  origin: the grid's low corner [3],
+    voxel: its cell size, dims = (nx, ny, nz).  A point lies in cell floor((p - origin) / voxel) per axis, in float64;
+    points outside the grid, with a non-finite coordinate, with a label outside [0, num_classes) or in a cell where
+    ``valid`` is 0 are not used.  *_labels: cuda integer [n] or None (every label 0); valid: cuda [nz,ny,nx] or None.
+
+    Returns (confusion int64 [C+1, C+1] -- row = state of the voxel in truth, column = in pred, state 0 = empty,
+    1 + c = occupied with majority label c (smallest label among equal votes); it sums to the number of valid cells
+    -- and info int64 [8] = m_truth, m_pred, points used of truth, of pred, bad labels of truth, of pred,
+    |truth n pred|, valid cells), both on the device: no host sync.  With return_cells also two tuples (cells int64
+    [m], labels int32 [m], counts int32 [m]), the occupied voxels of truth and of pred in ascending cell key
+    (ix + nx*iy + nx*ny*iz); that costs the one host sync that reads m."""
+    what = "voxel_confusion"
+    a, b = _xyz64(truth, "truth"), _xyz64(pred, "pred")
+    if a.device != b.device:
+        raise ValueError("truth and pred must be on the same device")
+    dev = a.device
+    org, voxel, d, C = _grid_args(origin, voxel, dims, num_classes, what)
+    na, nb = a.shape[0], b.shape[0]
+    la, lb = _labels_i32(truth_labels, na, dev, "truth_labels"), _labels_i32(pred_labels, nb, dev, "pred_labels")
+    if valid is not None:
+        if d[0] * d[1] * d[2] > 2 ** 31:
+            raise ValueError(f"{what}: a valid mask needs a grid of at most 2^31 cells")
+        valid = _mask_u8(valid, (d[2], d[1], d[0]), "valid")
+        if valid.device != dev:
+            raise ValueError("valid must be on the clouds' device")
+    L = _lib.lib()
+    ws = _workspace("voxel_iou", na, nb, C, device=dev)
+    with torch.cuda.device(dev):
+        conf = torch.empty(C + 1, C + 1, dtype=torch.int64, device=dev)
+        info = torch.empty(8, dtype=torch.int64, device=dev)
+        cells = [None] * 6
+        if return_cells:
+            cells = [torch.empty(n, dtype=dt, device=dev) for n in (na, nb)
+                     for dt in (torch.int64, torch.int32, torch.int32)]
+        opt = lambda t: _lib.ptr(t) if t is not None and t.numel() else None
+        _lib.check(L.sdp_voxel_iou(opt(a), na, a.shape[1], opt(la), opt(b), nb, b.shape[1], opt(lb),
+                                   (_lib.D * 3)(*org), voxel, (_lib.C.c_int64 * 3)(*d), C, _lib.ptr(valid),
+                                   conf.data_ptr(), *(opt(t) for t in cells), info.data_ptr(), ws.data_ptr(),
+                                   ws.numel(), _lib.stream()), "voxel_iou")
+        if return_cells:
+            ma, mb = (int(v) for v in info[:2].tolist())
+            return conf, info, tuple(t[:ma] for t in cells[:3]), tuple(t[:mb] for t in cells[3:])
+    return conf, info
+
+
+def iou_from_confusion(conf, ignore=()):
+    """Completion and semantic IoU from a ``voxel_confusion`` matrix [C+1, C+1] (tensor or array), on the host.
+
+    Occupancy over the states > 0: TP = voxels occupied in both, FP = only in the prediction (row 0), FN = only
+    in the truth (column 0); iou = TP / (TP + FP + FN), precision = TP / (TP + FP), recall = TP / (TP + FN), NaN
+    where the denominator is 0.  class_iou[c] = conf[1+c][1+c] / (row + column - diagonal) over the full matrix, NaN
+    where that union is 0; miou = the mean over the classes not in ``ignore`` whose union is non-zero, NaN if there
+    are none.  Returns a dict with these and the integers tp, fp, fn."""
+    m = conf.detach().cpu().numpy() if torch.is_tensor(conf) else np.asarray(conf)
+    if m.ndim != 2 or m.shape[0] != m.shape[1] or m.shape[0] < 2:
+        raise ValueError(f"iou_from_confusion expects a [C+1, C+1] matrix, got {m.shape}")
+    m = m.astype(np.int64)
+    C = m.shape[0] - 1
+    ignore = {int(c) for c in ignore}
+    if any(not 0 <= c < C for c in ignore):
+        raise ValueError(f"ignore must name classes in [0, {C})")
+    tp, fp, fn = int(m[1:, 1:].sum()), int(m[0, 1:].sum()), int(m[1:, 0].sum())
+    ratio = lambda num, den: num / den if den else float("nan")
+    diag = np.diagonal(m)[1:]
+    union = m.sum(1)[1:] + m.sum(0)[1:] - diag
+    class_iou = np.full(C, np.nan)
+    np.divide(diag, union, out=class_iou, where=union > 0)
+    keep = [c for c in range(C) if c not in ignore and union[c] > 0]
+    return {"iou": ratio(tp, tp + fp + fn), "precision": ratio(tp, tp + fp), "recall": ratio(tp, tp + fn),
+            "tp": tp, "fp": fp, "fn": fn, "class_iou": class_iou,
+            "miou": float(np.mean(class_iou[keep])) if keep else float("nan")}
+
+
+def voxel_iou(truth, pred, origin, voxel, dims, truth_labels=None, pred_labels=None, num_classes=1, valid=None,
+              ignore=()):
+    """``iou_from_confusion`` of ``voxel_confusion``: the completion IoU (and, with labels, per-class IoU / mIoU)
+    of ``pred`` against ``truth`` on the given grid.  The dict also holds "confusion" and "info" as host arrays.
+    One host sync, to read the matrix."""
+    conf, info = voxel_confusion(truth, pred, origin, voxel, dims, truth_labels, pred_labels, num_classes, valid)
+    host = torch.cat((conf.reshape(-1), info)).cpu().numpy()
+    out = iou_from_confusion(host[:-8].reshape(conf.shape), ignore)
+    out["confusion"], out["info"] = host[:-8].reshape(conf.shape), host[-8:]
+    return out
+
+
+def volume_to_cloud(labels_volume, origin, voxel, empty=0):
+    """A dense label volume [nz,ny,nx] (the SSC ground-truth form; tensor or array, any device) as a labelled
+    cloud: for every voxel whose label differs from ``empty`` its centre origin + (i + 0.5) * voxel (float64
+    [m,3], in ascending cell key) and its label (int32 [m]), on the volume's device.  On the SSC grid every centre
+    falls back into its own cell under ``voxel_confusion``'s arithmetic (tests/test_voxel_iou_ref_cpu.py)."""
+    vol = torch.as_tensor(labels_volume)
+    if vol.dim() != 3:
+        raise ValueError(f"volume_to_cloud expects a [nz,ny,nx] volume, got {tuple(vol.shape)}")
+    org = torch.as_tensor(np.asarray(origin, dtype=np.float64).reshape(3), device=vol.device)
+    idx = torch.nonzero(vol != empty)                      # [m,3] (iz, iy, ix), row-major = ascending key
+    pts = org + (idx.flip(1).to(torch.float64) + 0.5) * float(voxel)
+    return pts, vol[idx[:, 0], idx[:, 1], idx[:, 2]].to(torch.int32)
 
 
 def fuse_views(x, origins=None, poses=None, keep=None, exist=None, min_range=1.5, geometry="dataset",
